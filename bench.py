@@ -331,6 +331,46 @@ def library_digest():
         return None
 
 
+DUMP_BYTES = 60 * 1000 * 1000      # --dump-outputs: payload of all the .npy files of a run (<= 64 MB with their headers)
+DUMP_PIECE_BYTES = 8 << 20          # a transform larger than this is sampled in pieces of this size
+
+
+def dump_outputs(N, dirpath, prefix, planes, dtype, shape, count, seed, budget):
+    """--dump-outputs: what the last timed step left in the output buffers `planes` (device pointers: [interleaved] or [re, im],
+    `count` transforms of `shape` each), as float32 / float64 arrays DIR/<prefix>out.npy or <prefix>out_re.npy / <prefix>out_im.npy.
+    The whole output when it fits `budget` bytes: shape [count, *shape] (+ [2] = re, im of complex points).  Otherwise a fixed sample
+    seeded by `seed`: whole transforms, or pieces of DUMP_PIECE_BYTES of them when one transform is larger, the first and the last one
+    always in it; shape [pieces, points per piece] (+ [2]).  Returns what was written (for the JSON line)."""
+    import numpy
+    size = int(numpy.prod(shape))
+    isz = dtype.itemsize
+    piece = size
+    while piece * isz * len(planes) > min(DUMP_PIECE_BYTES, budget // 2) and piece % 2 == 0:
+        piece //= 2
+    total = count * size // piece
+    k = min(total, max(1, budget // (piece * isz * len(planes))))
+    if k == total:
+        picks = numpy.arange(total)
+    else:
+        rng = numpy.random.default_rng(seed)
+        inner = rng.choice(numpy.arange(1, total - 1), size=max(0, k - 2), replace=False) if total > 2 else []
+        picks = numpy.unique(numpy.concatenate([[0, total - 1], inner]).astype(numpy.int64))
+    rdtype = numpy.float32 if dtype in (numpy.complex64, numpy.float32) else numpy.float64
+    names = ["out"] if len(planes) == 1 else ["out_re", "out_im"]
+    for name, ptr in zip(names, planes):
+        host = numpy.empty((len(picks), piece), dtype)
+        if k == total:
+            N.check(N.lib.mifft_memcpy_d2h(host.ctypes.data, ptr, host.nbytes, None), "d2h")
+        else:
+            for row, p in enumerate(picks):
+                N.check(N.lib.mifft_memcpy_d2h(host[row].ctypes.data, ptr + int(p) * piece * isz, piece * isz, None), "d2h")
+        lead = ((count,) + tuple(shape)) if k == total else (len(picks), piece)
+        arr = host.view(rdtype).reshape(lead + ((2,) if dtype.kind == "c" else ()))
+        numpy.save(os.path.join(dirpath, prefix + name + ".npy"), arr)
+    return {"files": [prefix + n + ".npy" for n in names], "whole": bool(k == total), "points_per_piece": piece,
+            "pieces": [int(p) for p in picks], "of": total}
+
+
 def stats(xs):
     xs = sorted(xs)
     n = len(xs)
@@ -397,14 +437,22 @@ def main_single_process(args, auto_steps=False):
     outs = [[None] * n for _ in range(nplanes)]
     blocks = []
     for i, ((start, count), d) in enumerate(zip(slices, devices)):
-        blk, host_re, host_im, host_c = make_host_block(shape, dtname, batch, seed, start)
+        blk, _, _, host_c = make_host_block(shape, dtname, batch, seed, start)
         blocks.append((blk, host_c))
         with _OnDevice(hip, d):
-            for pl, host in enumerate((host_re, host_im) if split else (host_c,)):
+            for pl in range(nplanes):
                 ins[pl][i] = DeviceArray((size * count,), dtype)
                 outs[pl][i] = ins[pl][i] if args.inplace else DeviceArray((size * count,), dtype)
-                fill_device(N, ins[pl][i].ptr, ins[pl][i].nbytes, host)
-        del host_re, host_im
+
+    def fill_inputs():
+        """every shard's slice of the synthetic data set into its input buffers"""
+        for i, d in enumerate(devices):
+            host_c = blocks[i][1]
+            with _OnDevice(hip, d):
+                for pl, host in enumerate((host_c.real, host_c.imag) if split else (host_c,)):
+                    fill_device(N, ins[pl][i].ptr, ins[pl][i].nbytes, numpy.ascontiguousarray(host))
+
+    fill_inputs()
 
     def step():
         if args.inplace:
@@ -470,6 +518,9 @@ def main_single_process(args, auto_steps=False):
         est_step_ms = timed(k) / k
     if auto_steps:
         args.steps = max(10, int(250.0 / max(1e-3, est_step_ms)) + 1)
+    if args.inplace:
+        sync_all()
+        fill_inputs()        # the spin-up transformed the input in place a clock-dependent number of times
     for _ in range(args.warmup):
         step()
     sync_all()
@@ -478,6 +529,13 @@ def main_single_process(args, auto_steps=False):
     sync_all()
     elapsed = time.perf_counter() - t0
     splan.finish()           # raises if a persistent kernel of any shard reported a dependency time-out
+    dumped = None
+    if args.dump_outputs:
+        dumped = []
+        for i, ((start, count), d) in enumerate(zip(slices, devices)):
+            with _OnDevice(hip, d):
+                dumped.append(dump_outputs(N, args.dump_outputs, "shard%d_" % i, [outs[pl][i].ptr for pl in range(nplanes)], dtype,
+                                           shape, count, (seed, i), DUMP_BYTES // n))
 
     strategies = splan.strategy(gb, inplace=bool(args.inplace))
     total_xforms = gb * args.steps
@@ -513,6 +571,8 @@ def main_single_process(args, auto_steps=False):
     }
     if note:
         result["note"] = note
+    if dumped is not None:
+        result["dump_outputs"] = dumped
     print(json.dumps(result))
     splan.close()
 
@@ -541,6 +601,9 @@ def main():
     ap.add_argument("--dump-dir", default=None,
                     help="every rank writes the output of the first and the last transform of its slice there as "
                          "xform_<global index>.npy (test: checked against numpy on the global dataset)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, a fixed seeded "
+                         "sample when the output is larger than 64 MB; the inputs are the same in every run with the same arguments)")
     ap.add_argument("--share-gpu", action="store_true",
                     help="rank r uses device r %% (visible devices): runs the real sharded path with more ranks than GPUs (test)")
     ap.add_argument("--single-process", action="store_true",
@@ -551,6 +614,8 @@ def main():
     ap.add_argument("--no-spin-up", action="store_true", help="skip the untimed clock spin-up in front of the warm-up steps (A/B)")
     args = ap.parse_args()
 
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
     if args.plain:
         args.repeats = 0
         args.no_cpu_baseline = True
@@ -626,6 +691,15 @@ def main():
     nel = size * batch
     resident = False
     chunks = 1
+
+    def fill_inputs():
+        """the synthetic data set into the input buffers (again, when an untimed phase transformed them in place)"""
+        if split:
+            fill_device(N, ins[0].ptr, ins[0].nbytes, numpy.ascontiguousarray(host_c.real))
+            fill_device(N, ins[1].ptr, ins[1].nbytes, numpy.ascontiguousarray(host_c.imag))
+        else:
+            fill_device(N, ins[0].ptr, ins[0].nbytes, host_c)
+
     if share_mode:
         # the whole per-GPU share resident, transformed IN PLACE chunk by chunk (256 GiB of the 288 GB; out of place would need 512)
         chunks = share // batch
@@ -633,7 +707,7 @@ def main():
             ins = [DeviceArray((size * share,), dtype)]
             outs = ins
             resident = True
-            fill_device(N, ins[0].ptr, ins[0].nbytes, host_c)
+            fill_inputs()
         except RuntimeError as e:
             # no room (a shared or smaller device): the streaming loop over ONE pair of reused chunk buffers, out of place
             sys.stderr.write("bench.py: the %d-transform share does not fit (%s): reusing one resident chunk\n" % (share, str(e)[:120]))
@@ -643,12 +717,11 @@ def main():
     elif split:
         ins = [DeviceArray((nel,), dtype), DeviceArray((nel,), dtype)]
         outs = ins if args.inplace else [DeviceArray((nel,), dtype), DeviceArray((nel,), dtype)]
-        fill_device(N, ins[0].ptr, ins[0].nbytes, host_re)
-        fill_device(N, ins[1].ptr, ins[1].nbytes, host_im)
+        fill_inputs()
     else:
         ins = [DeviceArray((nel,), dtype)]
         outs = ins if args.inplace else [DeviceArray((nel,), dtype)]
-        fill_device(N, ins[0].ptr, ins[0].nbytes, host_c)
+        fill_inputs()
     del host_re, host_im
 
     plan = Plan(shape if len(shape) > 1 else shape[0], dtype=dtype, wait_for_finish=False)
@@ -664,15 +737,17 @@ def main():
     _trace("device buffers filled, plan built")
     stream = plan._context.getQueue()
 
-    def execute(inplace, inverse=False):
+    def execute(inplace, inverse=False, on=None):
+        """one execute over the batch: ins -> outs, or in place on `on` (default: ins)"""
+        bufs = on if on is not None else ins
         if split:
             if inplace:
-                plan.execute(ins[0], ins[1], batch=batch, inverse=inverse)
+                plan.execute(bufs[0], bufs[1], batch=batch, inverse=inverse)
             else:
                 plan.execute(ins[0], ins[1], outs[0], outs[1], batch=batch, inverse=inverse)
         else:
             if inplace:
-                plan.execute(ins[0], batch=batch, inverse=inverse)
+                plan.execute(bufs[0], batch=batch, inverse=inverse)
             else:
                 plan.execute(ins[0], outs[0], batch=batch, inverse=inverse)
 
@@ -830,7 +905,9 @@ def main():
                 e0, e1 = Event(), Event()
                 e0.record(stream)
                 for j in range(per):
-                    execute(inpl, inverse=bool(inpl and (j & 1)))
+                    # in place on the OUTPUT buffers: `per` follows the clock, and round trips on the input would leave the timed
+                    # steps a data set that differs from run to run in the last bits
+                    execute(inpl, inverse=bool(inpl and (j & 1)), on=outs)
                 e1.record(stream)
                 e1.synchronize()
                 ms.append(e1.time_since(e0) / per)
@@ -844,6 +921,9 @@ def main():
                               "strategy": plan.strategy(batch, inplace=inpl)[0]}
 
     # ---- warm-up, then EXACTLY K timed steps bracketed by barrier + device sync on both sides
+    if args.inplace or resident:
+        sync_all()
+        fill_inputs()           # the spin-up transformed the input in place a clock-dependent number of times
     for w in range(args.warmup):
         if resident:
             execute_chunk(w % chunks)
@@ -865,6 +945,12 @@ def main():
     elapsed = time.perf_counter() - t0
     dev_ms = ev1.time_since(ev0)          # HIP events on the stream the kernels are launched on
     plan.finish()                          # raises if a persistent kernel reported a dependency time-out (results invalid)
+    dumped = None
+    if args.dump_outputs:
+        # the last step's output: resident, the chunk it transformed in place
+        last = [ins[0].ptr + ((args.steps - 1) % chunks) * chunk_bytes] if resident else [o.ptr for o in outs]
+        dumped = dump_outputs(N, args.dump_outputs, "rank%d_" % rank if world > 1 else "", last, dtype, shape, batch,
+                              (seed, rank), DUMP_BYTES // world)
 
     rank_report = None
     if dist is not None:
@@ -1010,6 +1096,8 @@ def main():
     }
     if c5_note is not None:
         result["config"].update(c5_note)
+    if dumped is not None:
+        result["dump_outputs"] = dumped
     if rank == 0:
         print(json.dumps(result))
     if dist is not None:

@@ -395,7 +395,7 @@ REGISTRY = {
         "test_plan_for_a_device_given_by_index": lambda p: [_c((4096,), C64, 4)],
         "test_device_properties_describe_the_memory_system": None,
         "test_plan_with_stream_and_context_index": lambda p: [_c((8192,), C64, 3)],
-        "test_eight_ranks_share_one_gpu": lambda p: [_c((1 << 20,), C64, 40)],
+        "test_four_ranks_share_one_gpu": lambda p: [_c((1 << 20,), C64, 40)],
         "test_captured_execute_replays_bit_identically": lambda p: [_c(p["shape"], p["dtype"], p["batch"])],
         "test_plans_of_four_host_threads_run_side_by_side": "threads",
         "test_torch_cuda_graph_around_execute": lambda p: [_c((1 << 18,), C64, 160)],

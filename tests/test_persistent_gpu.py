@@ -10,7 +10,7 @@ import numpy
 import pytest
 
 import pyfft_oracle as oracle
-from helpers import EPS_F, MAX_F, _execute, _execute_split, _noise, _test_data
+from helpers import EPS_F, MAX_F, _execute, _execute_split, _noise, _test_data, run_on_dev_build
 
 pytestmark = pytest.mark.gpu
 
@@ -55,13 +55,14 @@ def test_async_error_mailbox(ctx):
 
 
 @pytest.mark.parametrize("dtype", [numpy.complex64, numpy.float32], ids=["interleaved", "split"])
-def test_xcd2_strategy_bit_identical_and_in_place(ctx, dtype, monkeypatch):
+def test_xcd2_strategy_bit_identical_and_in_place(ctx, dtype, monkeypatch, request):
     """The XCD-cooperative kernel (csrc/fft_xcd2.hpp, development strategy 'xcd'): bit-identical to the chain strategy,
     forward and inverse, out of place and in place (it needs no temp buffer), and its error word stays clear.  The kernel is part
     of `make DEV=1` builds of the library only (mifft_has_feature)."""
     from pyfft_amd import _native as N
-    if N.lib.mifft_has_feature(N.FEATURE_XCD2) != 1:
-        pytest.skip("development strategy: not in the default build of libmifft.so (make DEV=1)")
+    if N.lib.mifft_has_feature(N.FEATURE_XCD2) != 1:          # development strategy: not in the default build of libmifft.so
+        run_on_dev_build(request.node.nodeid)
+        return
     n, batch = 1 << 20, 72
     split = numpy.dtype(dtype).kind == "f"
     rng = numpy.random.default_rng(77)
@@ -162,13 +163,14 @@ def test_fused_pair_cube_128(ctx, monkeypatch, dtype, batch):
 
 # ---- per-XCD work lists as a default ---------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n,batch", [(1 << 16, 1040), (1 << 17, 520)], ids=str)
-def test_per_xcd_lists(ctx, monkeypatch, n, batch):
+def test_per_xcd_lists(ctx, monkeypatch, n, batch, request):
     """The fused kernel with one work list per XCD (mifft_launch_fused2x; pyfft/kernel.py:259-283 chain semantics), on request
     (within round 4 the 32-column tiles of the global list overtook it at 2^17): the bits of the chain, in place == out of place; a
     batch that is not a multiple of 8 leaves the lists uneven, work stealing drains them."""
     from pyfft_amd import _native as N
-    if N.lib.mifft_has_feature(N.FEATURE_FUSED2X) != 1:
-        pytest.skip("development strategy: not in the default build of libmifft.so (make DEV=1)")
+    if N.lib.mifft_has_feature(N.FEATURE_FUSED2X) != 1:       # development strategy: not in the default build of libmifft.so
+        run_on_dev_build(request.node.nodeid)
+        return
     if not ctx.hip.Machine.from_props(ctx.hip.device_props()).xcd_cooperative:
         pytest.skip("needs 8 XCDs x 32 CUs")
     data = _test_data((n,), numpy.complex64, batch, 91)
@@ -205,14 +207,15 @@ def test_fused_ring_rule_2_19(ctx, monkeypatch):
                                                ((128, 128, 128), numpy.complex64, 2), ((128, 128, 128), numpy.complex128, 1),
                                                ((1024, 1024), numpy.complex128, 2), ((1 << 22,), numpy.complex64, 1)],
                          ids=lambda v: str(numpy.dtype(v).name) if isinstance(v, type) else str(v).replace(" ", ""))
-def test_sequential_single_launch_of_tiny_batches(ctx, monkeypatch, shape, dtype, batch):
+def test_sequential_single_launch_of_tiny_batches(ctx, monkeypatch, shape, dtype, batch, request):
     """The reference's own benchmark protocol runs 32 MiB buffers (test/test_performance.py:11,22-30): there the two passes of a
     transform are two dependent launches.  The sequential work list runs them in ONE persistent launch (lag 0: every first-pass
     tile, then every second-pass tile); it must give the chain's bits, in place and out of place, forward and inverse.  Measured
     slower than the two launches (docs/negative_results.md): part of `make DEV=1` builds of the library only."""
     from pyfft_amd import _native as N
-    if N.lib.mifft_has_feature(N.FEATURE_SEQUENTIAL_LIST) != 1:
-        pytest.skip("development form: not in the default build of libmifft.so (make DEV=1)")
+    if N.lib.mifft_has_feature(N.FEATURE_SEQUENTIAL_LIST) != 1:   # development form: not in the default build of libmifft.so
+        run_on_dev_build(request.node.nodeid)
+        return
     data = _test_data(shape, dtype, batch, 93)
     monkeypatch.setenv("PYFFT_AMD_SMALL_FUSED", "0")
     want = _execute(ctx, shape, dtype, batch, data, expect="chain")

@@ -5,11 +5,11 @@
 # gpurun_out/<tag>/to_profiles/ under their final names -- back in the build container:
 #     cp gpurun_out/<tag>/to_profiles/* profiles/;  rocprofv3 gets the program directly after `--` (no env/bash hop), counters in their own runs.
 set -u
+export TMPDIR=/tmp && cd "$(dirname "$(readlink -f "$0")")/.."
 TAG=${1:-r06}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT/to_profiles profiles
 P=$OUT/to_profiles
-cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-/root/repo}"
 
 # 1. kernel stats + PMC traffic of the same command, per configuration (writes profiles/traffic_<c>.json and
 #    profiles/<tag>_<c>_kernel_stats.csv)

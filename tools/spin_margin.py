@@ -6,7 +6,9 @@ word ("results invalid") instead of hanging the GPU (csrc/fft_fused2.hpp, fused_
 work-group can be descheduled for a long time; this tool measures the margin.  `make DEV=1` builds of the library record, per counter
 set, the LONGEST wait of any work-group in polls (word 2 of the ticket line); run with PYFFT_AMD_DEV_BUILD=1:
 
-    PYFFT_AMD_DEV_BUILD=1 python3 tools/spin_margin.py            # one process alone, then 2 / 4 / 8 processes sharing the GPU
+    PYFFT_AMD_DEV_BUILD=1 python3 tools/spin_margin.py            # one process alone, then 2 / 4 processes sharing the GPU
+
+(At most four workers at once: a GPU shared with other work must not have more than six processes holding it open.)
 
 Every process runs the persistent kernel of BASELINE configuration 2's shape (2^20 points, batch 64 x 14 executes), configuration 5's
 (2^22, batch 16) and the two-pair cube kernel (128^3, batch 64) and prints the longest wait it saw.
@@ -65,7 +67,7 @@ def main():
     if N.lib.mifft_has_feature(N.FEATURE_FUSED2X) != 1:
         raise SystemExit("needs the development library: make -C pyfft_amd/csrc DEV=1 and PYFFT_AMD_DEV_BUILD=1")
     print("longest dependency wait of the persistent kernels in polls of ~1 us; the time-out is %d polls" % LIMIT, flush=True)
-    for procs in (1, 2, 4, 8):
+    for procs in (1, 2, 4):
         print("## %d process(es) on one GPU" % procs, flush=True)
         ps = [subprocess.Popen([sys.executable, os.path.abspath(__file__), "worker", "%d/%d" % (i, procs)]) for i in range(procs)]
         rc = [p.wait() for p in ps]
