@@ -8,9 +8,12 @@ collects (about half of the pass-pair instances had their only 
 
   keys_of(shape, dtype, batch, mode)   the instance keys one test case exercises, computed with the planner itself on the model
                                        of the full part (256 CUs, 8 XCDs, 256 MiB last-level cache) -- no device needed
+  keys_of_plan(plan, batch, mode)      the same for a given plan (a device plan: what the device's planner selects)
   universe()                           every key reachable by SOME power-of-two shape of up to 2^24 points in the four dtypes
   collected_cases()                    the (shape, dtype, batch, mode) cases of the default-collected GPU tests, read off the
                                        tests' own parametrize marks through REGISTRY (one adapter per test function)
+  audit_cases()                        for every key of universe(), the smallest case (shape, dtype, batch >= 3) that selects it: the
+                                       cases of tests/test_instances_gpu.py, which holds each instance to the accuracy contract
 
 The reference sweeps its kernels the same way, by shape lists: test/test_errors.py:125-145.
 """
@@ -22,7 +25,8 @@ import numpy
 from helpers import FakeContext
 
 GPU_MODULES = ["test_errors_gpu", "test_full_size_gpu", "test_functionality_gpu", "test_random_sweep_gpu", "test_rows_gpu",
-               "test_strided_gpu", "test_persistent_gpu", "test_pairs_gpu", "test_nd_gpu", "test_generic_gpu", "test_interop_gpu"]
+               "test_strided_gpu", "test_persistent_gpu", "test_pairs_gpu", "test_nd_gpu", "test_generic_gpu", "test_interop_gpu",
+               "test_instances_gpu"]
 
 C64, C128, F32, F64 = numpy.complex64, numpy.complex128, numpy.float32, numpy.float64
 ALL_DTYPES = [C64, F32, C128, F64]
@@ -174,7 +178,11 @@ def keys_of(shape, dtype, batch, mode="auto"):
     """Instance keys the test case (shape, dtype, batch) exercises.  mode: "auto" = the plan's own strategy at this batch, in place and
     out of place (what the tests' protocols run); "chain" / "pipelined" = the chain's launches; "fused" = the plan's persistent launch
     whatever the batch (PYFFT_AMD_STRATEGY=fused, or a forced ring)."""
-    plan = plan_for(shape, dtype)
+    return keys_of_plan(plan_for(shape, dtype), batch, mode)
+
+
+def keys_of_plan(plan, batch, mode="auto"):
+    """keys_of for a given plan: one on the model of the full part (plan_for), or a device plan (what that device's planner selects)"""
     keys = set()
     if mode in ("chain", "pipelined"):
         return _chain_keys(plan, plan._kernels)
@@ -215,10 +223,11 @@ DEV_ONLY_PAIR_KEYS = {("pairXY", "f64", "interleaved", 256, 64, 4), ("pairYZ", "
 MAX_LOG2_POINTS = 24          # shapes of up to 2^24 points: 4096 x 4096, 256^3, 2^24 (128 MiB fp32 / 256 MiB fp64 per transform)
 
 
-def universe(max_log=MAX_LOG2_POINTS):
-    """{key: an example (shape, dtype, batch)} over every power-of-two shape of up to 2^max_log points (x contiguous; numpy shapes
-    (z, y, x)), the four dtypes, and batches of 512 MiB, 2 GiB and 8 GiB per side -- where the planner's default choices live."""
-    out = {}
+UNIVERSE_SIDES = (512 << 20, 2 << 30, 8 << 30)
+
+
+def _shapes(max_log):
+    """every power-of-two shape of up to 2^max_log points (x contiguous; numpy shapes (z, y, x))"""
     for lx in range(0, max_log + 1):
         for ly in range(0, max_log + 1 - lx):
             for lz in range(0, max_log + 1 - lx - ly):
@@ -226,15 +235,90 @@ def universe(max_log=MAX_LOG2_POINTS):
                     continue
                 if (ly == 0 and lz > 0) or (lx == 0 and (ly > 0 or lz > 0)):
                     continue            # (unit axes in front of longer ones are the same plans as the lower-rank shape: tests cover them by name)
-                shape = (1 << lx,) if ly == 0 else ((1 << ly, 1 << lx) if lz == 0 else (1 << lz, 1 << ly, 1 << lx))
-                for dtype in ALL_DTYPES:
-                    item = (1 << (lx + ly + lz)) * (8 if dtype in (C64, F32) else 16)
-                    for side in (512 << 20, 2 << 30, 8 << 30):
-                        batch = max(1, side // item)
-                        for k in keys_of(shape, dtype, batch):
-                            if k is not None and k not in out:
-                                out[k] = (shape, numpy.dtype(dtype).name, batch)
-    return out
+                yield (1 << lx,) if ly == 0 else ((1 << ly, 1 << lx) if lz == 0 else (1 << lz, 1 << ly, 1 << lx))
+
+
+def _item_bytes(shape, dtype):
+    return _prod(shape) * (8 if dtype in (C64, F32) else 16)
+
+
+_universe = {}
+
+
+def universe(max_log=MAX_LOG2_POINTS):
+    """{key: an example (shape, dtype, batch)} over every power-of-two shape of up to 2^max_log points (x contiguous; numpy shapes
+    (z, y, x)), the four dtypes, and batches of 512 MiB, 2 GiB and 8 GiB per side -- where the planner's default choices live."""
+    if max_log in _universe:
+        return dict(_universe[max_log])
+    out = {}
+    for shape in _shapes(max_log):
+        for dtype in ALL_DTYPES:
+            item = _item_bytes(shape, dtype)
+            for side in UNIVERSE_SIDES:
+                batch = max(1, side // item)
+                for k in keys_of(shape, dtype, batch):
+                    if k is not None and k not in out:
+                        out[k] = (shape, numpy.dtype(dtype).name, batch)
+    _universe[max_log] = out
+    return dict(out)
+
+
+# ---- one audit case per instance key (tests/test_instances_gpu.py) -------------------------------------------------------------------
+AUDIT_MIN_BATCH = 3
+_audit = {}
+
+
+def audit_cases(max_log=MAX_LOG2_POINTS):
+    """[(shape, dtype name, batch, keys)]: for every key of universe() but DEV_ONLY_PAIR_KEYS, the smallest case (bytes per side) that
+    selects it with batch >= 3, in a batch that is no multiple of 4 where the key allows one (tiles that hold several transforms then end
+    partially filled); a case that is the smallest for several keys appears once, `keys` sorted.  Per (shape, dtype) the planner is asked
+    at batch 3 and at universe()'s batches; a key that only appears at a larger batch is bisected down to the batch where it appears.
+    A key without such a case raises (the audit must not silently lose an instance)."""
+    if max_log in _audit:
+        return list(_audit[max_log])
+    uni = universe(max_log)
+    want = set(uni) - DEV_ONLY_PAIR_KEYS
+    best = {}                       # key -> (bytes, order, shape, dtype, batch)
+    order = 0
+    for shape in _shapes(max_log):
+        for dtype in ALL_DTYPES:
+            item = _item_bytes(shape, dtype)
+            memo = {}
+
+            def keys_at(b):
+                if b not in memo:
+                    memo[b] = set(k for k in keys_of(shape, dtype, b) if k in want)
+                return memo[b]
+
+            probes = sorted(set([AUDIT_MIN_BATCH] + [max(AUDIT_MIN_BATCH, side // item) for side in UNIVERSE_SIDES]))
+            prev = None
+            for b in probes:
+                for k in keys_at(b):
+                    if (prev is not None and k in keys_at(prev)) or (k in best and best[k][0] <= AUDIT_MIN_BATCH * item):
+                        continue        # (recorded at the previous probe; or no batch of this shape beats the case found)
+                    lo, hi = prev, b
+                    while lo is not None and hi - lo > 1:
+                        mid = (lo + hi) // 2
+                        if k in keys_at(mid):
+                            hi = mid
+                        else:
+                            lo = mid
+                    if hi % 4 == 0 and k in keys_at(hi + 1):
+                        hi += 1
+                    order += 1
+                    cand = (hi * item, order, shape, numpy.dtype(dtype).name, hi)
+                    if k not in best or cand[0] < best[k][0]:
+                        best[k] = cand
+                prev = b
+    missing = sorted(want - set(best), key=str)
+    if missing:
+        raise AssertionError("tests/kernel_coverage.py audit_cases: no case with batch >= %d selects %r" % (AUDIT_MIN_BATCH, missing[:40]))
+    cases = {}
+    for k, (_, _, shape, dtname, batch) in best.items():
+        cases.setdefault((shape, dtname, batch), []).append(k)
+    out = sorted(((shape, dtname, batch, tuple(sorted(ks, key=str))) for (shape, dtname, batch), ks in cases.items()), key=lambda c: str(c[3][0]))
+    _audit[max_log] = out
+    return list(out)
 
 
 # ---- the default-collected GPU cases, read off the tests' parametrize marks ----------------------------------------------------------
@@ -401,6 +485,9 @@ REGISTRY = {
         "test_torch_cuda_graph_around_execute": lambda p: [_c((1 << 18,), C64, 160)],
         "test_sharded_plan_two_shards_on_one_device": lambda p: [_c(p["shape"], p["dtype"], p["batch"] // 2)],
         "test_bench_single_process_four_shards_share_one_gpu": lambda p: [_c((1 << 20,), C64, 40)],
+    },
+    "test_instances_gpu": {
+        "test_instance": lambda p: [_c(p["case"][0], numpy.dtype(p["case"][1]).type, p["case"][2])],
     },
 }
 
