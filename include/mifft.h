@@ -41,8 +41,10 @@ extern "C" {
 /* 2: mifft_launch_fused2's counter buffer is MIFFT_FUSED2_COUNTER_BYTES (one 256-byte line per counter) and is zeroed by the
  * call; streams are blocking streams; mifft_stream_wait_event
  * 3: the persistent launches take a mifft_fused_sync: two alternating counter sets, error word anywhere the device can write;
- * mifft_device_props carries the last-level cache size and the XCD count; mifft_launch_fused_pair */
-#define MIFFT_ABI_VERSION 5
+ * mifft_device_props carries the last-level cache size and the XCD count; mifft_launch_fused_pair
+ * 6: mifft_has_feature, mifft_launch_xcd2 and mifft_launch_fused2x are gone; debug keys 1, 4 and 11 are retired; the persistent
+ * launchers refuse lag == 0 */
+#define MIFFT_ABI_VERSION 6
 
 /* negative library error codes (positive values are hipError_t) */
 #define MIFFT_E_INVALID      (-1)  /* malformed descriptor / argument              */
@@ -153,22 +155,19 @@ int         mifft_abi_version(void);
 const char *mifft_last_error(void);
 /* development switches (all 0 in production; pyfft_amd/_debug.py maps environment variables onto them) */
 #define MIFFT_DEBUG_NO_ND2 0       /* run-time-shaped N-D kernel only */
-#define MIFFT_DEBUG_FUSED_NO_NT 1  /* fused two-pass kernel without non-temporal hints */
 #define MIFFT_DEBUG_NO_WAVE 2      /* no wave-autonomous small-transform kernels */
 #define MIFFT_DEBUG_FORCE_WAVE 3   /* wave-autonomous kernels wherever one exists, whatever the buffer size */
-#define MIFFT_DEBUG_PERSIST 4      /* persistent (prefetching) form of the long fp32 rows (measured: no gain) */
 #define MIFFT_DEBUG_ALT_ROWS 5     /* alternative stage lists of the longest fp32 rows (A/B measurements) */
 #define MIFFT_DEBUG_PAIR 6         /* pass pairs: 0 = default split, 1 = off, 2 = the alternative y split, 3 = the first tile forms of the persistent two-pair kernel (A/B measurements) */
 #define MIFFT_DEBUG_STORE 7        /* streamed output stores (A/B): 0 = default, 1 = non-temporal, 2 = write-through (sc1), 3 = plain */
 #define MIFFT_DEBUG_ROWS_ND 8      /* dense smooth rows: 0 = default, 1 = two-buffer row kernel only, 2 = single-buffer tile kernel wherever it fits (A/B) */
 #define MIFFT_DEBUG_NARROW_TILES 9 /* A/B of the round-4 tile forms: 1 = the rounds 1-3 forms -- fp32 L = 256 / 512 on 16-column tiles also in the persistent
                                     * kernel, and for split-complex planes no lane-interleaved double tiles, no register-edged rows, no fixed-shape N-D
-                                    * route, no row-first 2-D kernel, no write-through in the run-time-shaped N-D kernel; 2 = 32-column tiles (and the
-                                    * double tile of a plane-writing L = 1024 pass) also in plain launches; 3 = 16-column tiles also for strided passes
+                                    * route, no row-first 2-D kernel, no write-through in the run-time-shaped N-D kernel; 3 = 16-column tiles also for strided passes
                                     * whose rows lie >= 2^16 points apart (round 6: those run on 32-column tiles by default) */
 #define MIFFT_DEBUG_NO_ROWFIRST 10 /* split-complex fp32 2-D persistent launches: 1 = two transposing passes on sibling tiles instead of the row-first kernel (A/B) */
-#define MIFFT_DEBUG_PREFETCH 11 /* persistent kernels on 512-thread tiles, `make DEV=1` builds: 1 = the work list that issues a tile's loads before the publish of
-                                  * the previous one (round 6; measured equal to the round-2 list: 0.392 / 0.393 on configuration 5) */
+/* keys 1, 4 and 11 are retired (they selected kernel forms that were measured and not adopted): mifft_debug_set and
+ * mifft_debug_set_default refuse them with MIFFT_E_INVALID */
 #define MIFFT_DEBUG_KEYS 12
 /* mifft_debug_set changes a switch for the CALLING THREAD only (a thread that never set a key sees the process default), so a
  * measurement that flips a switch in one thread cannot change the kernels another thread's plan gets; mifft_debug_set_default sets
@@ -178,17 +177,6 @@ const char *mifft_last_error(void);
 int mifft_debug_set(int32_t key, int32_t value);
 int mifft_debug_set_default(int32_t key, int32_t value);
 int mifft_debug_get(int32_t key);
-/* Optional parts of the library.  The default build leaves out the measured-and-not-adopted strategies (`make DEV=1` builds them):
- * their launchers then return MIFFT_E_UNSUPPORTED and mifft_has_feature says so beforehand. */
-#define MIFFT_FEATURE_XCD2 0            /* mifft_launch_xcd2: XCD-resident single-crossing form of 1024 x 1024 (0.32-0.34 against 0.44) */
-#define MIFFT_FEATURE_FUSED2X 1         /* mifft_launch_fused2x: one work list per XCD */
-#define MIFFT_FEATURE_SEQUENTIAL_LIST 2 /* lag == 0 in the persistent launchers: both passes of a tiny batch in one launch */
-#define MIFFT_FEATURE_AB_FORMS 3        /* the kernel forms only the development switches select (A/B measurements): 16-column tiles for
-                                         * every length and unpaired plane tiles in the persistent kernels (MIFFT_DEBUG_NARROW_TILES = 1),
-                                         * plain / write-through streams (MIFFT_DEBUG_FUSED_NO_NT, MIFFT_DEBUG_STORE), persistent and
-                                         * alternative long rows (MIFFT_DEBUG_PERSIST, MIFFT_DEBUG_ALT_ROWS), the two-transposing-pass form
-                                         * of split-complex 2-D squares; without it such a request fails with MIFFT_E_UNSUPPORTED */
-int mifft_has_feature(int32_t feature); /* 1 = built in, 0 = not */
 
 /* ---- runtime shim (replaces cuda.py Context: allocate / stream lifecycle / device limits) ---------- */
 int mifft_device_count(int *count);
@@ -352,27 +340,10 @@ typedef struct mifft_fused_sync {
     void *counters_next;
     void *error_word;
 } mifft_fused_sync;
-/* lag == 0 selects the SEQUENTIAL work list for tiny batches (ring_slots == outer): every first-pass tile of every transform,
- * then every second-pass tile -- two dependent launches folded into one, without the launch gap and the end-of-kernel
- * write-back between them (the reference's own 32 MiB benchmark protocol, test/test_performance.py:11,22-30).  Development form
- * (MIFFT_FEATURE_SEQUENTIAL_LIST; measured slower than two launches): the list is dealt out statically, which is deadlock-free
- * only while EVERY work-group of the launch is resident -- the launcher caps the grid by the kernel's occupancy on this device,
- * but it cannot see other streams, processes or CU masks, so the device must be the caller's alone; otherwise the bounded waits
- * time out (~4 s per item), the error word is set and the output is invalid. */
+/* 1 <= lag < ring_slots, MIFFT_E_INVALID otherwise */
 int mifft_launch_fused2(const mifft_pass *p0, const mifft_pass *p1, const void *in0, const void *in1, void *out0,
                         void *out1, void *ring0, void *ring1, int32_t ring_slots, int32_t lag, const mifft_fused_sync *sync,
                         int32_t grid, mifft_stream_t stream);
-
-/*
- * The same launch with one work list PER XCD (strategy `fusedx`, csrc/fft_fused2.hpp): XCD x owns the transforms x, x + 8, ... and
- * the ring slots [x * ring_slots, (x + 1) * ring_slots), so the ring holds 8 * ring_slots transforms.  A work-group whose own
- * list is exhausted drains the other XCDs' lists, so the result does not depend on where the work-groups land (the
- * intermediate is written write-through, like the global form's).  fp32 1-D pairs with p0->L >= p1->L in {256, 512, 1024};
- * in1 / out1 = the imaginary planes of split-complex user buffers (NULL for interleaved data; the ring is always interleaved).
- */
-int mifft_launch_fused2x(const mifft_pass *p0, const mifft_pass *p1, const void *in0, const void *in1, void *out0, void *out1,
-                         void *ring0, int32_t ring_slots, int32_t lag, const mifft_fused_sync *sync, int32_t grid,
-                         mifft_stream_t stream);
 
 /*
  * Persistent form of a 3-D plan made of two PASS PAIRS (mifft_pair_split > 0): passes[0..3] = ROW x | COL y (R0) | COL y (R1) |
@@ -393,32 +364,6 @@ int mifft_fused_pair_supported(int32_t precision, int32_t layout, int32_t x, int
 int mifft_fused_pair_split(int32_t precision, int32_t layout, int32_t x, int32_t y, int32_t z);
 int mifft_launch_fused_pair(const mifft_pass *passes, const void *in0, const void *in1, void *out0, void *out1, void *ring0,
                             int32_t ring_slots, int32_t lag, const mifft_fused_sync *sync, int32_t grid, mifft_stream_t stream);
-
-/*
- * XCD-cooperative form of the same two-pass axis for N = 1024 * 1024, fp32 (csrc/fft_xcd2.hpp): ONE persistent launch of
- * 2 work-groups per CU in which the 64 work-groups resident on each XCD (chiplet) own one transform at a time and
- * hand the inter-pass intermediate over through that XCD's own L2, so that every point crosses the L2 <-> fabric
- * boundary once in and once out (the fused / chained forms: twice).  Same pass pair as mifft_launch_fused2.
- *   scratch  caller-owned, MIFFT_XCD2_SCRATCH_BYTES, 256-byte aligned; contents are don't-care
- *   control  caller-owned, MIFFT_XCD2_CONTROL_BYTES (zeroed by this call on `stream`).  After completion
- *            ((uint32_t*)control)[1] != 0 means the results are INVALID: bit 0 = a bounded wait timed out, bit 1 = the
- *            launch did not find exactly 64 resident work-groups per XCD (nothing was written; run another strategy).
- *   flags    bit 0: issue the next transform's loads while the current one is being stored (default form)
- *            bit 1 (development): `control` is MIFFT_XCD2_CONTROL_BYTES + MIFFT_XCD2_TRACE_BYTES long and receives, behind
- *            the control words, 32 time stamps (100 MHz) per work-group for the per-XCD transform index (flags >> 8)
- *            bits 4..6 (development): elimination variant 1..5 of csrc/fft_xcd2.hpp -- same launch with a part of the work
- *            removed; the results are WRONG by construction (profiles/r03_xcd2_elimination.log)
- *            bits 8..23 the traced transform index; bits 24..30 (development, round 5): the XCDs with an odd id start that many
- *            microseconds late (anti-phase HBM bursts, profiles/r05_xcd2_antiphase.log); results unchanged
- * Requires a device with 8 XCDs x 32 CUs (MI355X); MIFFT_E_UNSUPPORTED otherwise or for other lengths.
- */
-#define MIFFT_XCD2_SCRATCH_BYTES (8u * 64u * 16u * 256u * 8u)
-#define MIFFT_XCD2_CONTROL_BYTES ((64u + 2u * 512u * 32u) * 4u) /* one 128-byte line per flag */
-#define MIFFT_XCD2_PREFETCH 1
-#define MIFFT_XCD2_TRACE 2
-#define MIFFT_XCD2_TRACE_BYTES (512u * 32u * 8u)
-int mifft_launch_xcd2(const mifft_pass *p0, const mifft_pass *p1, const void *in0, const void *in1, void *out0,
-                      void *out1, void *scratch, void *control, int32_t flags, mifft_stream_t stream);
 
 /*
  * ---- extensions the reference lists as TODO (TODO.txt:6-8): tiles of a bigger array, sizes that are not powers of two ----

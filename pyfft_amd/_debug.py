@@ -7,7 +7,7 @@ import os
 
 
 def forced_strategy():
-    """PYFFT_AMD_STRATEGY = auto | chain | pipelined | fused | fusedx | xcd"""
+    """PYFFT_AMD_STRATEGY = auto | chain | pipelined | fused"""
     return os.environ.get("PYFFT_AMD_STRATEGY", "auto")
 
 
@@ -63,16 +63,6 @@ def fused_memset():
     return bool(os.environ.get("PYFFT_AMD_FUSED_MEMSET"))
 
 
-def no_fusedx():
-    """PYFFT_AMD_NO_FUSEDX=1: never choose the per-XCD work lists by default (A/B)"""
-    return bool(os.environ.get("PYFFT_AMD_NO_FUSEDX"))
-
-
-def split_fusedx():
-    """PYFFT_AMD_SPLIT_FUSEDX=1: split-complex fp32 N = 2^16 ... 2^18 on the per-XCD work lists (A/B; the default is the sibling-tile kernel on the global list)"""
-    return bool(os.environ.get("PYFFT_AMD_SPLIT_FUSEDX"))
-
-
 def no_split_rowfirst():
     """PYFFT_AMD_NO_SPLIT_ROWFIRST=1: split-complex fp32 2-D plans keep the round-3 rule (pipelined chunks; two transposing passes on
     request).  The launcher picks the kernel too, so the calling thread's native switch follows the variable whenever the planner asks."""
@@ -112,30 +102,11 @@ def fused3_lag_ring(lag, ring):
     return lag, ring
 
 
-def fusedx():
-    """PYFFT_AMD_FUSEDX = lag,ring (per XCD) of the XCD-local fused form forced by PYFFT_AMD_STRATEGY=fusedx (a third field,
-    round 3's write-through switch, is accepted and ignored)"""
-    v = os.environ.get("PYFFT_AMD_FUSEDX", "1,2,0")
-    return tuple(int(t) for t in v.split(","))
-
-
-def small_fused(default):
-    """PYFFT_AMD_SMALL_FUSED = lag divisor of the small-batch fused form (0 = off)"""
-    v = os.environ.get("PYFFT_AMD_SMALL_FUSED")
-    return default if v is None else int(v)
-
-
-def xcd2_flags(default):
-    v = os.environ.get("PYFFT_AMD_XCD2_FLAGS")
-    return default if v is None else int(v)
-
-
 def apply_native_switches(native):
     """Environment -> the process defaults of libmifft's development switches (mifft_debug_set_default); called once when the library
     is loaded.  (mifft_debug_set itself changes a switch for the calling thread only: tests and tools use that.)"""
-    for env, key in (("MIFFT_NO_ND2", native.DEBUG_NO_ND2), ("MIFFT_FUSED_NO_NT", native.DEBUG_FUSED_NO_NT),
-                     ("MIFFT_NO_WAVE", native.DEBUG_NO_WAVE), ("MIFFT_FORCE_WAVE", native.DEBUG_FORCE_WAVE),
-                     ("MIFFT_PERSIST", native.DEBUG_PERSIST)):
+    for env, key in (("MIFFT_NO_ND2", native.DEBUG_NO_ND2), ("MIFFT_NO_WAVE", native.DEBUG_NO_WAVE),
+                     ("MIFFT_FORCE_WAVE", native.DEBUG_FORCE_WAVE)):
         if os.environ.get(env):
             native.lib.mifft_debug_set_default(key, 1)
     if os.environ.get("MIFFT_STORE"):       # streamed output stores: 1 = non-temporal, 2 = write-through, 3 = plain
@@ -144,8 +115,6 @@ def apply_native_switches(native):
         native.lib.mifft_debug_set_default(native.DEBUG_ROWS_ND, int(os.environ["MIFFT_ROWS_ND"]))
     if os.environ.get("MIFFT_NARROW_TILES"):   # fp32 2^16 ... 2^18 persistent: 16-column tiles (A/B)
         native.lib.mifft_debug_set_default(native.DEBUG_NARROW_TILES, int(os.environ["MIFFT_NARROW_TILES"]))
-    if os.environ.get("MIFFT_PREFETCH"):    # persistent kernels on 512-thread tiles (development builds): the loads-first work list of round 6 (A/B)
-        native.lib.mifft_debug_set_default(native.DEBUG_PREFETCH, 1)
     if os.environ.get("MIFFT_PAIR"):        # pass pairs: 1 = off, 2 = the alternative y split
         native.lib.mifft_debug_set_default(native.DEBUG_PAIR, int(os.environ["MIFFT_PAIR"]))
     # the row-first switch steers the planner AND the launcher: the process default follows the environment here, so that a plan

@@ -10,10 +10,9 @@ import ctypes
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# PYFFT_AMD_DEV_BUILD=1: the `make DEV=1` library (development strategies and A/B kernel forms, pyfft_amd/csrc/Makefile)
-LIB_PATH = os.path.join(_HERE, "libmifft_dev.so" if os.environ.get("PYFFT_AMD_DEV_BUILD") else "libmifft.so")
+LIB_PATH = os.path.join(_HERE, "libmifft.so")
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 E_INVALID = -1
 E_UNSUPPORTED = -2
@@ -32,8 +31,6 @@ FLAG_SRC_INTERLEAVED, FLAG_DST_INTERLEAVED = 1, 2
 FLAG_STREAM_SRC, FLAG_STREAM_DST = 4, 8
 FLAG_WRITE_THROUGH = 32
 FLAG_PAIR_WITH_NEXT = 16
-XCD2_SCRATCH_BYTES = 8 * 64 * 16 * 256 * 8
-XCD2_CONTROL_BYTES = (64 + 2 * 512 * 32) * 4
 FUSED2_COUNTER_STRIDE = 64          # MIFFT_FUSED2_COUNTER_STRIDE (uint32 words between two counters)
 
 
@@ -42,15 +39,11 @@ def fused2_counter_bytes(outer):
     return FUSED2_COUNTER_STRIDE * 4 * (9 + 2 * int(outer))
 
 
-XCD2_PREFETCH = 1
-DEBUG_NO_ND2, DEBUG_FUSED_NO_NT, DEBUG_NO_WAVE, DEBUG_FORCE_WAVE, DEBUG_PERSIST, DEBUG_ALT_ROWS, DEBUG_PAIR, DEBUG_STORE = 0, 1, 2, 3, 4, 5, 6, 7
+DEBUG_NO_ND2, DEBUG_NO_WAVE, DEBUG_FORCE_WAVE, DEBUG_ALT_ROWS, DEBUG_PAIR, DEBUG_STORE = 0, 2, 3, 5, 6, 7
 DEBUG_ROWS_ND = 8
 DEBUG_NARROW_TILES = 9
 DEBUG_NO_ROWFIRST = 10
-DEBUG_PREFETCH = 11
-FEATURE_XCD2, FEATURE_FUSED2X, FEATURE_SEQUENTIAL_LIST, FEATURE_AB_FORMS = 0, 1, 2, 3     # mifft_has_feature: parts only `make DEV=1` builds
-XCD2_TRACE = 2
-XCD2_TRACE_BYTES = 512 * 32 * 8
+DEBUG_KEYS = 12     # MIFFT_DEBUG_KEYS; keys 1, 4 and 11 are retired (mifft_debug_set refuses them)
 
 
 class MifftPass(ctypes.Structure):
@@ -151,7 +144,6 @@ PROTOTYPES = {
     "mifft_debug_set": (ctypes.c_int, [_i32, _i32]),
     "mifft_debug_set_default": (ctypes.c_int, [_i32, _i32]),
     "mifft_debug_get": (ctypes.c_int, [_i32]),
-    "mifft_has_feature": (ctypes.c_int, [_i32]),
     "mifft_device_count": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)]),
     "mifft_set_device": (ctypes.c_int, [ctypes.c_int]),
     "mifft_get_device": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)]),
@@ -193,11 +185,9 @@ PROTOTYPES = {
     "mifft_launch_chain_pipelined": (ctypes.c_int, [_pass_p, _i32, _vpp, _vpp, ctypes.c_int64, ctypes.c_int64,
                                                       ctypes.c_int64, _vp, _vpp, _i32, _vpp]),
     "mifft_launch_fused2": (ctypes.c_int, [_pass_p, _pass_p, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _sync_p, _i32, _vp]),
-    "mifft_launch_fused2x": (ctypes.c_int, [_pass_p, _pass_p, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _sync_p, _i32, _vp]),
     "mifft_fused_pair_supported": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32]),
     "mifft_fused_pair_split": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32]),
     "mifft_launch_fused_pair": (ctypes.c_int, [_pass_p, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _sync_p, _i32, _vp]),
-    "mifft_launch_xcd2": (ctypes.c_int, [_pass_p, _pass_p, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "mifft_nd_tiled_supported": (ctypes.c_int, [_i32, _i32, _i32, _i32]),
     "mifft_launch_nd_tiled": (ctypes.c_int, [_pass_p, ctypes.POINTER(MifftTiling), _vp, _vp, _vp]),
     "mifft_launch_nd_tiled_split": (ctypes.c_int, [_pass_p, ctypes.POINTER(MifftTiling), _vp, _vp, _vp, _vp, _vp]),

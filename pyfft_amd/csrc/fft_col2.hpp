@@ -32,7 +32,7 @@ template <int A, int E, typename T> __device__ __forceinline__ cplx<T> mul_w16A(
 
 // The 15 table twiddles s^k of a first stage, s = w(L)^i0: four look-ups (k = 1, 2, 4, 8) plus products of at most three of
 // them, the high ones formed on demand (saves ~14 VGPRs against 15 look-ups held across the stage).  `step` = table entries per
-// unit of i0 (1 when the table is w(L') of the sub-transform, 2 when it is w(2L')).  Shared by fft_col3.hpp and fft_xcd2.hpp;
+// unit of i0 (1 when the table is w(L') of the sub-transform, 2 when it is w(2L')).  Used by fft_col3.hpp;
 // col2_tile below spells the same arithmetic out in place.
 template <typename T> struct ColStageTw {
     cplx<T> s1, s2, s3, s4, s5, s6, s7, s8;

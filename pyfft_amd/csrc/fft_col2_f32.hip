@@ -39,8 +39,7 @@ extern "C" int mifft_col2_f32_eligible(int L, int tr, const mifft::TileArgs* a) 
 // be 32 whole columns of one matrix and the column pair adjacent in the output (S >= 2 in the plain form).  In the PERSISTENT kernel
 // they are worth 3-6 points (fft_fused2w_kernel); as plain launches of the chain / the pipelined chunks they measure within +- 2 %
 // of the 16-column tiles, in both directions (profiles/r04_r_plain_wide_tiles_ab.log: 2^16 x 512 0.395 / 0.399, 2^18 x 64
-// 0.336 / 0.357, (512, 512) x 128 0.372 / 0.351, pipelined 2^16 0.405 / 0.397), so the plain launches keep the 16 columns; the
-// instances stay for the A/B: MIFFT_DEBUG_NARROW_TILES = 2 runs them wherever they fit.
+// 0.336 / 0.357, (512, 512) x 128 0.372 / 0.351, pipelined 2^16 0.405 / 0.397), so the plain launches keep the 16 columns.
 //
 // Round 6: ONE exception -- rows that lie far apart.  The plain strided pass along the z axis of a 3-D transform of hundreds of MiB (or
 // the last pass of N = 2^24) gathers its 256 / 512 rows 512 KiB ... 2 MiB apart; 128-byte segments at that distance stream at 0.55 of
@@ -58,22 +57,6 @@ bool wide_far_ok(int L, int tr, const mifft::TileArgs* a) {
     return !tr && (L == 256 || L == 512) && !a->split && !a->split_out && sw != 1 && sw != 3 &&
            (a->total & 31) == 0 && a->logMS >= 5 && a->logS >= 16;
 }
-#ifdef MIFFT_DEV_BUILD      // (A/B instances: `make DEV=1`, MIFFT_FEATURE_AB_FORMS)
-template <int A> int launch_w(int tr, const mifft::TileArgs* a, hipStream_t s) {
-    const long long tiles = a->total / 32;
-    if (tiles > 2147483647ll) return -1;
-    const dim3 g((unsigned)tiles), b(256);
-    if (tr) hipLaunchKernelGGL((mifft::fft_col2w_kernel<A, true, true>), g, b, 0, s, *a);
-    else hipLaunchKernelGGL((mifft::fft_col2w_kernel<A, false, false>), g, b, 0, s, *a);
-    return (int)hipGetLastError();
-}
-bool wide_ok(int L, int tr, const mifft::TileArgs* a) {
-    if (L != 256 && L != 512) return false;
-    if (a->split || a->split_out || mifft_debug_get(MIFFT_DEBUG_NARROW_TILES) != 2) return false;
-    if ((a->total & 31) || a->logMS < 5 || (!tr && a->logS < 1)) return false;
-    return a->total / 32 >= 1024;
-}
-#endif
 }  // namespace
 
 extern "C" int mifft_col2x_f32_eligible(int L, int tr, const mifft::TileArgs* a);   // fft_col2x_f32.hip
@@ -81,9 +64,6 @@ extern "C" int mifft_col2x_f32_launch(int L, int tr, const mifft::TileArgs* a, h
 
 extern "C" int mifft_col2_f32_launch(int L, int tr, const mifft::TileArgs* a, hipStream_t s) {
     if (mifft_col2x_f32_eligible(L, tr, a)) return mifft_col2x_f32_launch(L, tr, a, s);   // split planes: whole lines per wave instruction
-#ifdef MIFFT_DEV_BUILD
-    if (wide_ok(L, tr, a)) return L == 512 ? launch_w<2>(tr, a, s) : launch_w<1>(tr, a, s);
-#endif
     if (wide_far_ok(L, tr, a)) return L == 512 ? launch_w_plain<2>(a, s) : launch_w_plain<1>(a, s);
     switch (L) {
         case 1024: return launch<4>(tr, a, s);

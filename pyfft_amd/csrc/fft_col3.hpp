@@ -74,8 +74,7 @@ __device__ __forceinline__ void col3_store_wt16(const char* base, unsigned voff,
 }
 
 // phase 1 of a tile on its own: v[a*16 + b1] = in[2*(b1*16A + a*16 + b0) + h][column c] -- 16 A loads per thread, all issued before
-// anything waits for them.  The persistent kernels of round 6 call it at the END of the previous tile (fft_fused2.hpp,
-// fused_list_prefetch), everything else from col3_tile below.
+// anything waits for them.  Called from col3_tile below.
 template <typename T, int A, bool SPLIT, bool NTIN>
 __device__ __forceinline__ void col3_load(const TileArgs& a, const long long o_in, const long long rem0, cplx<T>* v) {
     constexpr int PPT = 16 * A;

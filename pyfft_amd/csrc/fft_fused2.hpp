@@ -28,18 +28,16 @@ namespace mifft {
 
 constexpr unsigned kFusedCS = 64u;   // words between two counters (= MIFFT_FUSED2_COUNTER_STRIDE)
 
-// the work list and its synchronisation state (shared by every persistent kernel: fft_fused2 / fused3 / fused2x / fusedp)
+// the work list and its synchronisation state (shared by every persistent kernel: fft_fused2 / fused3 / fusedp)
 struct FusedCtl {
     unsigned* counters;  // [0] ticket, [1] error (when `err` points here), then one counter per CS = 64 words (256 bytes): wdone[t] at
-                         // CS * (1 + t), rdone[t] at CS * (1 + batch + t), the ticket counters of the per-XCD lists behind them; ALL ZERO
-                         // when the launch starts
+                         // CS * (1 + t), rdone[t] at CS * (1 + batch + t); ALL ZERO when the launch starts
     unsigned* counters_next;   // nullptr, or a second counter set that THIS launch zeroes for the next one (round 4: a plan alternates
                                // between two sets, so no memset node precedes the launch)
     unsigned* err;       // error word, set on a dependency time-out (device-accessible: counters + 1, or pinned host memory)
     unsigned lines;      // counter lines per set (9 + 2 * batch)
     unsigned batch;      // number of transforms
-    unsigned lag;        // pass 1 of transform t is queued with pass 0 of transform t + lag; 0 = the SEQUENTIAL list of a tiny batch:
-                         // every pass-0 tile of every transform, then every pass-1 tile (ring = batch slots, no slot is reused)
+    unsigned lag;        // pass 1 of transform t is queued with pass 0 of transform t + lag; 1 <= lag < ring (the launchers refuse 0)
     unsigned ring;       // scratch ring slots (transforms); ring > lag
     unsigned tiles0;     // tiles per transform in pass 0
     unsigned tiles1;     // tiles per transform in pass 1
@@ -51,28 +49,11 @@ struct FusedArgs {
     FusedCtl c;
 };
 
-// XCD-local form (strategy `fusedx`, round 3; a default since round 4): one work list PER XCD (chiplet).  A work-group reads its XCD
-// from HW_REG_XCC_ID and draws tickets from that XCD's counter; XCD x owns the transforms t = x + 8 i, its ring slots are
-// [x * ring, (x + 1) * ring).  (Round 3 measured that the intermediate still crosses the fabric twice -- an XCD's L2 keeps ~1 MiB
-// next to the streams, a stall-free list needs 4-32 MiB -- so what the form buys is eight short pipelines with eight ticket
-// counters instead of one long one: + 2 points at 2^16 / 2^17, profiles/r04_a_fused_sweep.log.)  Same dependency order per list, so
-// the same no-deadlock argument.  Round 4: a work-group that finds its own list exhausted moves on to the lists other XCDs have
-// not finished (work stealing, in list order), so every list is drained whatever the placement of the work-groups -- a launch
-// that leaves an XCD without work-groups (a CU mask, a shared device) is slower, not wrong.
-__device__ __forceinline__ unsigned fused_xcc_id() {
-    unsigned v;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v));
-    return v & 7u;
-}
-
 // Deferred publish of a pass-0 tile: its write-through stores drain under the first poll of the NEXT item's dependency, and
 // the counter is bumped BEFORE this work-group starts to wait.  (Publishing only after the wait has ended deadlocks: work-group
 // X owes a tile of transform T and waits for U while Y owes a tile of U and waits for T -- measured as dependency time-outs.)
 struct FusedPending {
     unsigned* ctr;   // wdone counter still to be bumped, or nullptr
-#ifdef MIFFT_DEV_BUILD
-    unsigned max_spins;   // `make DEV=1`: the longest dependency wait of this work-group in polls (tools/spin_margin.py)
-#endif
 };
 
 // wait until *ctr >= target (one lane polls, bounded); ACQ: also make other work-groups' published data visible.
@@ -97,9 +78,6 @@ template <bool ACQ> __device__ __forceinline__ void fused_wait_ge(unsigned* ctr,
                 break;
             }
         }
-#ifdef MIFFT_DEV_BUILD
-        if (spins > pend.max_spins) pend.max_spins = spins;
-#endif
         if constexpr (ACQ) {
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -142,16 +120,13 @@ struct FusedItem {
     unsigned target;
 };
 
-// xs = 8 and x = the XCD for the XCD-local lists (group g of the list = transform x + 8 g, `nb` = transforms of this list);
-// xs = 1, x = 0, nb = batch for the one global list.  it.t is the GLOBAL transform, it.slot its ring slot.
+// it.t is the transform, it.slot its ring slot
 template <unsigned PER0, unsigned PER1>
-__device__ __forceinline__ FusedItem fused_decode(const FusedCtl& f, unsigned item, unsigned gsize, unsigned* wdone, unsigned* rdone,
-                                                  unsigned x = 0u, unsigned xs = 1u, unsigned nb = 0xffffffffu) {
+__device__ __forceinline__ FusedItem fused_decode(const FusedCtl& f, unsigned item, unsigned gsize, unsigned* wdone, unsigned* rdone) {
     FusedItem it;
     it.dep = nullptr;
     it.target = 0;
-    if (f.lag == 0u) {
-        // sequential list (tiny batches): no empty item, no ring reuse; a pass-1 tile still waits for its transform's pass-0 tiles
+    if (f.lag == 0u) {   // unreachable (the launchers refuse lag == 0); removing it changes the kernels: a follow-up with measurements
         const unsigned n0 = f.batch * f.tiles0;
         if (item < n0) {
             it.pass = 0u;
@@ -169,20 +144,19 @@ __device__ __forceinline__ FusedItem fused_decode(const FusedCtl& f, unsigned it
     }
     constexpr unsigned period = PER0 + PER1;
     const unsigned g = item / gsize, k = item % gsize, j = k / period, m = k % period;
-    if (xs == 1u) nb = f.batch;
     if (m < PER0) {
-        it.pass = g < nb ? 0u : 2u;
-        it.t = x + xs * g;
-        it.slot = x * f.ring * (xs >> 3) + g % f.ring;
+        it.pass = g < f.batch ? 0u : 2u;
+        it.t = g;
+        it.slot = g % f.ring;
         it.tile = j * PER0 + m;
         if (it.pass == 0u && g >= f.ring) {
-            it.dep = rdone + kFusedCS * (x + xs * (g - f.ring));   // the ring slot it overwrites has been read
+            it.dep = rdone + kFusedCS * (g - f.ring);   // the ring slot it overwrites has been read
             it.target = f.tiles1;
         }
     } else {
         it.pass = g >= f.lag ? 1u : 2u;
-        it.t = x + xs * (g - f.lag);
-        it.slot = x * f.ring * (xs >> 3) + (g - f.lag) % f.ring;
+        it.t = g - f.lag;
+        it.slot = (g - f.lag) % f.ring;
         it.tile = j * PER1 + (m - PER0);
         if (it.pass == 1u) {
             it.dep = wdone + kFusedCS * it.t;           // every pass-0 tile of the transform has published
@@ -192,11 +166,7 @@ __device__ __forceinline__ FusedItem fused_decode(const FusedCtl& f, unsigned it
     return it;
 }
 
-// lane 0 only: hand out this item's ticket and its early poll, draw the next ticket.  `stat`: the sequential list of a tiny batch is
-// dealt out STATICALLY (work-group w takes the items w, w + grid, ...): with every work-group of the launch resident (grid <= 2 per
-// CU, checked by the host) nothing can deadlock -- a work-group runs all its first-pass items, which never wait, before its first
-// second-pass item -- and 512 work-groups do not queue up twice at one ticket counter (measured: 53 against 25 us for two plain
-// launches at (1024, 1024) x 4 with tickets, profiles/r04_b_small_batch_sequential.log).
+// lane 0 only: hand out this item's ticket and its early poll, draw the next ticket.  (`stat`: lag == 0, unreachable.)
 __device__ __forceinline__ unsigned fused_advance(FusedQueue& q, unsigned& seen, unsigned total, unsigned* next, bool stat) {
     const unsigned item = q.t1;
     seen = q.seen1;
@@ -212,20 +182,19 @@ template <unsigned PER0, unsigned PER1> struct FusedHook {
     FusedQueue& q;
     unsigned total, gsize;
     unsigned *wdone, *rdone;
-    unsigned x, xs, nb;
     __device__ __forceinline__ void operator()() const {
         if (threadIdx.x == 0 && q.t1 < total) {
-            const FusedItem nx = fused_decode<PER0, PER1>(f, q.t1, gsize, wdone, rdone, x, xs, nb);
+            const FusedItem nx = fused_decode<PER0, PER1>(f, q.t1, gsize, wdone, rdone);
             if (nx.dep != nullptr) q.seen1 = __hip_atomic_load(nx.dep, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
 };
 
-// one work list (the global one, or the list of XCD x), drained by this work-group together with whoever else draws from `next`
+// the work list, drained by this work-group together with every other one
 template <unsigned PER0, unsigned PER1, bool EARLY, typename TILE0, typename TILE1>
-__device__ __forceinline__ void fused_list(const FusedCtl& f, unsigned* s_item, TILE0& tile0, TILE1& tile1, FusedPending& pend,
-                                           const unsigned x, const unsigned xs, const unsigned nb, unsigned* const next) {
+__device__ __forceinline__ void fused_list(const FusedCtl& f, unsigned* s_item, TILE0& tile0, TILE1& tile1, FusedPending& pend) {
     unsigned* const err = f.err;
+    unsigned* const next = f.counters;
     // One counter per 256-byte line: the counters of the few transforms in flight are polled and bumped by all 512 work-groups,
     // and packed 32 to a line they shared one memory channel's atomic unit (C2 with no polls at all -- wrong results, same
     // traffic -- ran 15 % faster; hiding the poll LATENCY changed nothing: it is the rate of same-line agent-scope accesses).
@@ -234,12 +203,12 @@ __device__ __forceinline__ void fused_list(const FusedCtl& f, unsigned* s_item, 
     // a group = the tiles0 pass-0 tiles of transform g and the tiles1 pass-1 tiles of transform g - lag, interleaved in their
     // ratio (tiles0 : tiles1 = PER0 : PER1), so that no ticket is an empty item
     const unsigned gsize = f.tiles0 + f.tiles1;
-    const unsigned total = f.lag == 0u ? f.batch * gsize : (nb + f.lag) * gsize;
+    const unsigned total = f.lag == 0u ? f.batch * gsize : (f.batch + f.lag) * gsize;   // (lag == 0: unreachable)
 
     const bool stat = f.lag == 0u;
     FusedQueue q = {0u, 0u};
     if (threadIdx.x == 0) q.t1 = stat ? blockIdx.x : __hip_atomic_fetch_add(next, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const FusedHook<PER0, PER1> hook = {f, q, total, gsize, wdone, rdone, x, xs, nb};
+    const FusedHook<PER0, PER1> hook = {f, q, total, gsize, wdone, rdone};
     for (;;) {
         __syncthreads();  // the previous item's LDS traffic and its s_item read are over
         unsigned seen = 0;
@@ -247,7 +216,7 @@ __device__ __forceinline__ void fused_list(const FusedCtl& f, unsigned* s_item, 
         __syncthreads();
         const unsigned item = *s_item;
         if (item >= total) break;
-        const FusedItem it = fused_decode<PER0, PER1>(f, item, gsize, wdone, rdone, x, xs, nb);
+        const FusedItem it = fused_decode<PER0, PER1>(f, item, gsize, wdone, rdone);
         if (it.pass == 2u) {             // fill / drain of the pipeline: nothing to do, but never sit on a publish
             fused_flush(pend);
             continue;
@@ -267,12 +236,11 @@ __device__ __forceinline__ void fused_list(const FusedCtl& f, unsigned* s_item, 
             fused_signal_read(rdone + kFusedCS * it.t);
         }
     }
-    fused_flush(pend);   // never carry a publish into another list (or out of the kernel)
+    fused_flush(pend);   // never carry a publish out of the kernel
 }
 
 // one persistent work-group: TILE0(t, slot, tile, hook) / TILE1(slot, t, tile, hook) run one tile of pass 0 / pass 1
-// XCD = 1: one work list per XCD, own list first, then the unfinished lists of the other XCDs.
-template <unsigned PER0, unsigned PER1, bool EARLY, typename TILE0, typename TILE1, int XCD = 0>
+template <unsigned PER0, unsigned PER1, bool EARLY, typename TILE0, typename TILE1>
 __device__ __forceinline__ void fused_loop(const FusedCtl& f, unsigned* s_item, TILE0&& tile0, TILE1&& tile1) {
     // the counter set of the NEXT launch (words 0 and 1 of every line: a counter, or ticket + error / census)
     if (f.counters_next != nullptr) {
@@ -282,45 +250,7 @@ __device__ __forceinline__ void fused_loop(const FusedCtl& f, unsigned* s_item, 
         }
     }
     FusedPending pend = {};
-    if constexpr (XCD == 0) {
-        fused_list<PER0, PER1, EARLY>(f, s_item, tile0, tile1, pend, 0u, 1u, f.batch, f.counters);
-#ifdef MIFFT_DEV_BUILD
-        // word 2 of the ticket line: the longest dependency wait of the launches on this counter set, in polls of ~1 us (the time-out is
-        // 2^22); nothing else writes it, and only a memset of the set clears it
-        if (threadIdx.x == 0 && pend.max_spins) __hip_atomic_fetch_max(f.counters + 2, pend.max_spins, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
-    } else {
-        // ticket counter of XCD x on its own line behind the dependency counters
-        const unsigned home = fused_xcc_id();
-        unsigned* const tickets = f.counters + kFusedCS * (1u + 2u * f.batch);
-        const unsigned gsize = f.tiles0 + f.tiles1;
-        unsigned visit = 1u;     // bit h: drain the list of XCD (home + h) & 7
-        for (unsigned h = 0; h < 8u; ++h) {
-            if (visit & (1u << h)) {
-                const unsigned x = (home + h) & 7u;
-                fused_list<PER0, PER1, EARLY>(f, s_item, tile0, tile1, pend, x, 8u, (f.batch + 7u - x) >> 3, tickets + kFusedCS * x);
-            }
-            if (h == 0u) {
-                // own list exhausted: which other lists still have tickets?  (seven loads in flight at once, one lane)
-                __syncthreads();
-                if (threadIdx.x == 0) {
-                    unsigned v[7];
-#pragma unroll
-                    for (unsigned k = 0; k < 7u; ++k)
-                        v[k] = __hip_atomic_load(tickets + kFusedCS * ((home + 1u + k) & 7u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    unsigned mask = 1u;
-#pragma unroll
-                    for (unsigned k = 0; k < 7u; ++k) {
-                        const unsigned x = (home + 1u + k) & 7u;
-                        if (v[k] < (((f.batch + 7u - x) >> 3) + f.lag) * gsize) mask |= 2u << k;
-                    }
-                    *s_item = mask;
-                }
-                __syncthreads();
-                visit = *s_item;
-            }
-        }
-    }
+    fused_list<PER0, PER1, EARLY>(f, s_item, tile0, tile1, pend);
 }
 
 // NT: 0 = plain accesses on the streamed side, 1 = non-temporal loads of the input and stores of the output, 2 = non-temporal
@@ -368,26 +298,6 @@ __global__ void __launch_bounds__(512, 2) fft_fused2s_kernel(const FusedArgs f) 
             asm volatile("" : "+v"(tid));
             col2_tile<float, A1, TWOD, false, false, false, false, NT, SPLIT, true>(f.p1, (long long)slot, (long long)t, (long long)item * 32, lds, hook, tid);
         });
-}
-
-// XCD-local lists (see fused_xcc_id above).  The intermediate is written WRITE-THROUGH, as in the global form: a work-group that
-// drains another XCD's list (work stealing) produces and consumes across XCDs, and only write-through stores + the consumer's
-// acquire are coherent between two L2s.  (Round 3's plain-store variant -- the intermediate in the owning XCD's L2 -- measured
-// 0-2 points more and was placement-dependent: removed.)
-template <typename T, int A0, int A1, bool SPLIT = false>
-__global__ void __launch_bounds__(256, 2) fft_fused2x_kernel(const FusedArgs f) {
-    constexpr int E0 = Col2Lds<A0, true, sizeof(cplx<T>)>::ELEMS, E1 = Col2Lds<A1, false, sizeof(cplx<T>)>::ELEMS;
-    __shared__ __attribute__((aligned(16))) cplx<T> lds[E0 > E1 ? E0 : E1];
-    __shared__ unsigned s_item;
-    constexpr unsigned per0 = A0 > A1 ? 1u : (unsigned)(A1 / A0);
-    constexpr unsigned per1 = A1 > A0 ? 1u : (unsigned)(A0 / A1);
-    auto t0 = [&](unsigned t, unsigned slot, unsigned tile, auto hook) {
-        col2_tile<T, A0, true, true, SPLIT, true, !SPLIT, false, false>(f.p0, (long long)t, (long long)slot, (long long)tile * 16, lds, hook);
-    };
-    auto t1 = [&](unsigned slot, unsigned t, unsigned tile, auto hook) {
-        col2_tile<T, A1, false, false, false, false, false, !SPLIT, SPLIT>(f.p1, (long long)slot, (long long)t, (long long)tile * 16, lds, hook);
-    };
-    fused_loop<per0, per1, !SPLIT, decltype(t0)&, decltype(t1)&, 1>(f.c, &s_item, t0, t1);
 }
 
 // The 1-D kernel on the 32-column tiles of fft_col2w.hpp (round 4): fp32 interleaved, L0 >= L1 in {256, 512} (N = 2^16 ... 2^18);
@@ -489,123 +399,6 @@ __global__ void __launch_bounds__(512, 2) fft_fused3_kernel(const FusedArgs f) {
         [&](unsigned slot, unsigned t, unsigned tile, auto hook) {
             col3_tile<T, A1, false, false, false, false, NT, SPLIT>(f.p1, (long long)slot, (long long)t, (long long)tile * 16, lds, hook);
         });
-}
-
-// ---- round 6: the next tile's loads issued at the END of the current tile ---------------------------------------------------------------
-// With one 512-thread work-group per CU nothing overlaps a tile's dead time: at the top of every item the work-group drains its stores
-// (publish), polls the item's dependency (an agent-scope load: 1-3 us), runs an acquire, and only then issues the tile's loads and waits
-// a memory latency for the first of them -- 4-5 us of a 21 us tile in which this CU moves no data (profiles/r06_fused3_counters.log:
-// 102 read requests in flight per L2 channel against 127 for the 256-thread kernel at two work-groups per CU).  Here thread 0 hands
-// out the NEXT item from inside the current tile's last exchange round (hook2: the round's own barrier publishes it to the work-group),
-// and the loop issues that item's loads FIRST, right behind the previous tile's last stores -- before the publish (store drain +
-// barrier + counter), which then runs concurrently with the load latency; no barrier and no LDS round trip lie between two tiles.  A second-pass item is prefetched only if the early poll of its
-// dependency (the hook in the middle of the tile) has already seen it satisfied -- thread 0 then runs the acquire in hook2, in front
-// of the barrier; otherwise the item takes the ordinary path at the top of the loop.  First-pass items read the user's input, which
-// depends on nothing (their dependency guards the ring slot they WRITE, and is still waited for before the tile computes).
-// Tickets stay global and increasing, every work-group still works through its tickets in order and publishes before it waits: the
-// no-deadlock argument of the list above is unchanged.  LOAD0(t, tile) / LOAD1(slot, tile) issue a tile's loads into the caller's registers.
-template <unsigned PER0, unsigned PER1, typename LOAD0, typename LOAD1, typename TILE0, typename TILE1>
-__device__ __forceinline__ void fused_list_prefetch(const FusedCtl& f, unsigned* s_item, LOAD0& load0, LOAD1& load1, TILE0& tile0, TILE1& tile1) {
-    unsigned* const err = f.err;
-    unsigned* const next = f.counters;
-    unsigned* const wdone = f.counters + kFusedCS;
-    unsigned* const rdone = wdone + kFusedCS * f.batch;
-    const unsigned gsize = f.tiles0 + f.tiles1;
-    const unsigned total = (f.batch + f.lag) * gsize;
-    FusedPending pend = {nullptr};
-    FusedQueue q = {0u, 0u};
-    unsigned seen_cur = 0;       // thread 0: the early poll of the CURRENT item's dependency
-    if (threadIdx.x == 0) {
-        s_item[0] = __hip_atomic_fetch_add(next, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_item[1] = 0u;
-        q.t1 = __hip_atomic_fetch_add(next, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    const FusedHook<PER0, PER1> hook = {f, q, total, gsize, wdone, rdone, 0u, 1u, f.batch};
-    // thread 0: hand out the next item (s_item[0]) and say whether its loads may be issued at once (s_item[1])
-    auto handout = [&]() {
-        if (threadIdx.x == 0) {
-            const unsigned nxt = q.t1;
-            unsigned ok = 0u;
-            seen_cur = q.seen1;
-            q.seen1 = 0u;
-            if (nxt < total) {
-                const FusedItem nx = fused_decode<PER0, PER1>(f, nxt, gsize, wdone, rdone);
-                if (nx.pass == 0u) {
-                    ok = 1u;
-                } else if (nx.pass == 1u && seen_cur >= nx.target) {
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    ok = 1u;
-                }
-                q.t1 = __hip_atomic_fetch_add(next, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            s_item[0] = nxt;
-            s_item[1] = ok;
-        }
-    };
-    for (;;) {
-        // (what thread 0 wrote in the previous tile's last round -- or in the prologue -- is visible: a barrier lies in between)
-        const unsigned item = __builtin_amdgcn_readfirstlane(s_item[0]);
-        const bool ok = __builtin_amdgcn_readfirstlane(s_item[1]) != 0u;
-        if (item >= total) break;
-        const FusedItem it = fused_decode<PER0, PER1>(f, item, gsize, wdone, rdone);
-        if (it.pass == 0u) {
-            load0(it.t, it.tile);                    // right behind the previous tile's last stores: the input depends on nothing
-            if (it.dep != nullptr) fused_wait_ge<false>(it.dep, it.target, seen_cur, err, pend);    // (the ring slot it WRITES is free)
-            else fused_flush(pend);
-            tile0(it.t, it.slot, it.tile, hook, handout);
-            pend.ctr = wdone + kFusedCS * it.t;     // published behind the next item's loads (or at the end)
-        } else if (it.pass == 1u) {
-            // ok: the early poll saw the dependency satisfied and thread 0 ran the acquire in front of the barrier that published this
-            // item; else the ordinary path -- publish what this work-group owes, THEN wait
-            if (!ok) fused_wait_ge<true>(it.dep, it.target, seen_cur, err, pend);
-            load1(it.slot, it.tile);
-            fused_flush(pend);
-            tile1(it.slot, it.t, it.tile, hook, handout);
-            fused_signal_read(rdone + kFusedCS * it.t);
-        } else {                          // fill / drain of the pipeline: nothing to do, but never sit on a publish
-            fused_flush(pend);
-            __syncthreads();             // (the previous hand-out has been read by everybody)
-            handout();
-            __syncthreads();
-        }
-    }
-    fused_flush(pend);
-}
-
-// fft_fused3_kernel with the prefetching list (interleaved data; A0 >= A1: the registers hold the larger tile)
-template <typename T, int A0, int A1, bool NT>
-__global__ void __launch_bounds__(512, 2) fft_fused3p_kernel(const FusedArgs f) {
-    constexpr int E0 = Col3Lds<T, true>::SCALARS, E1 = Col3Lds<T, false>::SCALARS;
-    __shared__ __attribute__((aligned(16))) T lds[E0 > E1 ? E0 : E1];
-    __shared__ unsigned s_item[2];
-    constexpr unsigned per0 = A0 > A1 ? 1u : (unsigned)(A1 / A0);
-    constexpr unsigned per1 = A1 > A0 ? 1u : (unsigned)(A0 / A1);
-    cplx<T> v[16 * (A0 > A1 ? A0 : A1)];
-    if (f.c.counters_next != nullptr) {      // the counter set of the NEXT launch (as fused_loop)
-        for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < f.c.lines; i += gridDim.x * blockDim.x) {
-            f.c.counters_next[i * kFusedCS] = 0u;
-            f.c.counters_next[i * kFusedCS + 1u] = 0u;
-        }
-    }
-    Col3StageTw<T, A0> st0;
-    Col3StageTw<T, A1> st1;
-    auto l0 = [&](unsigned t, unsigned tile) {
-        col3_load<T, A0, false, NT>(f.p0, (long long)t, (long long)tile * 16, v);
-        st0.load(f.p0);
-    };
-    auto l1 = [&](unsigned slot, unsigned tile) {
-        col3_load<T, A1, false, false>(f.p1, (long long)slot, (long long)tile * 16, v);
-        st1.load(f.p1);
-    };
-    auto t0 = [&](unsigned t, unsigned slot, unsigned tile, auto hook, auto hook2) {
-        col3_body<T, A0, true, true, false, false, true>(f.p0, (long long)slot, (long long)tile * 16, lds, v, st0, hook, hook2);
-    };
-    auto t1 = [&](unsigned slot, unsigned t, unsigned tile, auto hook, auto hook2) {
-        col3_body<T, A1, false, false, NT, false, false>(f.p1, (long long)t, (long long)tile * 16, lds, v, st1, hook, hook2);
-    };
-    fused_list_prefetch<per0, per1>(f.c, s_item, l0, l1, t0, t1);
 }
 
 // 2-D shapes on the 512-thread tiles (axis length 512 * A): fp64 1024 x 1024 (the published double-precision shape), fp32 with a

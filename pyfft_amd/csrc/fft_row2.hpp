@@ -134,7 +134,7 @@ struct Row2Stages<T, L, TPR, Ns, FIRST, HALF, RadixList<R, Rest...>, LAY> {
     // PRELOADED: v already holds the row (persistent form: loaded behind the previous row's stores).
     // FirstStage / (next_inb, next_valid): persistent form only -- the LAST stage issues the NEXT row's first-stage loads into
     // the registers of every butterfly right behind that butterfly's stores, so that they fly under the remaining
-    // butterflies and stores of this row (one row fills the CU: there is no second work-group to overlap with).
+    // butterflies and stores of this row.  (The persistent row kernel measured no gain and is gone; no kernel sets these.)
     template <bool PRELOADED = false, typename FirstStage = void>
     static __device__ __forceinline__ void run(LdsT* lds, cplx<T>* v, const TileArgs& a, int tid, const char* inb,
                                                char* outb, unsigned voff, bool valid, const char* next_inb = nullptr,
@@ -284,56 +284,6 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(OCC))) 
     }
     cplx<T> v[PPT];
     Row2Stages<T, L, TPR, 1, true, HALF, RL, LAY>::run(lds + c * LP, v, a, u, inb, outb, voff, valid, nullptr, false, inb1, outb1);
-}
-
-// Persistent form for the rows that fill a CU (W == 1, one work-group per CU or two): the work-group walks rows
-// blockIdx.x, blockIdx.x + gridDim.x, ...; the first-stage loads of the next row are issued from the last stage of the
-// current one (Row2Stages::run, FirstStage).
-template <typename T, int L, int NT, bool HALF, int OCC, typename RL>
-__global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(OCC))) fft_row2p_kernel(const TileArgs a) {
-    constexpr int PPT = L / NT;
-    constexpr int LP = L + L / 16;
-    using LdsT = typename std::conditional<HALF, T, cplx<T>>::type;
-    using First = Row2Stages<T, L, NT, 1, true, HALF, RL>;
-    __shared__ __attribute__((aligned(16))) LdsT lds[LP];
-    const unsigned voff = (unsigned)threadIdx.x * (unsigned)sizeof(cplx<T>);
-    long long row = blockIdx.x;
-    if (row >= a.total) return;
-    cplx<T> v[PPT];
-    {
-        const char* inb = reinterpret_cast<const char*>(reinterpret_cast<const cplx<T>*>(a.in0) + row * a.ostride_in);
-        First::template load_regs<0, PPT, false>(v, inb, voff);
-    }
-    for (;;) {
-        const long long next = row + gridDim.x;
-        // (the strides are laundered per row so that the ~PPT row offsets are not hoisted out of the loop as SGPR pairs)
-        long long sin = a.ostride_in, sout = a.ostride_out;
-        asm volatile("" : "+s"(sin), "+s"(sout));
-        int tid = threadIdx.x;
-        asm volatile("" : "+v"(tid));
-        const char* inb = reinterpret_cast<const char*>(reinterpret_cast<const cplx<T>*>(a.in0) + row * sin);
-        char* outb = reinterpret_cast<char*>(reinterpret_cast<cplx<T>*>(a.out0) + row * sout);
-        const char* nin = reinterpret_cast<const char*>(reinterpret_cast<const cplx<T>*>(a.in0) + next * sin);
-        First::template run<true, First>(lds, v, a, tid, inb, outb, (unsigned)tid * (unsigned)sizeof(cplx<T>), true, nin, next < a.total);
-        if (next >= a.total) break;
-        row = next;
-        __syncthreads();   // the last exchange's LDS reads are over before the next row's first spill
-    }
-}
-
-// blocks_per_cu: resident work-groups per CU of this configuration (LDS- or register-bound); the grid is that many per CU
-template <typename T, int L, int NT, typename RL, bool HALF, int OCC>
-static inline int launch_row2p(const TileArgs* a, hipStream_t s, int blocks_per_cu) {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-    }
-    long long grid = (long long)cus * blocks_per_cu;
-    if (grid > a->total) grid = a->total;
-    if (grid <= 0) return 0;
-    hipLaunchKernelGGL((fft_row2p_kernel<T, L, NT, HALF, OCC, RL>), dim3((unsigned)grid), dim3(NT), 0, s, *a);
-    return (int)hipGetLastError();
 }
 
 template <typename T, int L, int W, int NT, typename RL, bool HALF = false, int OCC = 1, int LAY = 0>

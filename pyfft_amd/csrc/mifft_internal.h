@@ -4,7 +4,6 @@
 #include "../../include/mifft.h"
 #include "fft_tile.hpp"
 #include "fft_fused2.hpp"
-#include "fft_xcd2.hpp"
 #include "fft_nd.hpp"
 #include "fft_wave.hpp"
 #include "fft_pair.hpp"
@@ -28,7 +27,6 @@ int mifft_fused2_f32_launch(int L0, int L1, const mifft::FusedArgs* f, int split
 int mifft_fused2dw_f32(int ny, int nx, const mifft::FusedArgs* f, unsigned grid, hipStream_t s, int query, unsigned* tiles0, unsigned* tiles1);
 int mifft_fused2r_f32(int ny, int nx, const mifft::FusedArgs* f, unsigned grid, hipStream_t s, int query);
 int mifft_fused2w_f32_launch(int L0, int L1, const mifft::FusedArgs* f, unsigned grid, hipStream_t s);
-int mifft_fused2x_f32_launch(int L0, int L1, const mifft::FusedArgs* f, int split, unsigned grid, hipStream_t s);
 int mifft_fused2d_f32_launch(int ny, int nx, const mifft::FusedArgs* f, int split, unsigned grid, hipStream_t s);
 int mifft_fused3d_f64_launch(int ny, int nx, const mifft::FusedArgs* f, int split, unsigned grid, hipStream_t s);
 int mifft_fusedx_f64(int L0, int L1, const mifft::FusedArgs* f, unsigned grid, hipStream_t s, int query, unsigned* tiles0, unsigned* tiles1);
@@ -65,7 +63,6 @@ int mifft_mixed_nd_launch(int f64, int nx, int ny, int nz, long long transforms,
                           const void* twz, int flags, double scale, hipStream_t s);
 int mifft_bluestein_launch(int f64, int n, int m, long long rows, long long stride_in, long long stride_out, const void* in, void* out,
                            const void* tw, const void* chirp, const void* bhat, int flags, double scale, hipStream_t s);
-int mifft_xcd2_f32_launch(const mifft::Xcd2Args* f, int split, int prefetch, int mode, unsigned grid, hipStream_t s);
 // fft_nd2z.hip: 0 = launched (query 1: a kernel exists; query 2: one that is preferred at every buffer size), -2 = none, -1 = grid too large
 int mifft_nd2z(int f64, int x, int y, int z, const mifft::TileArgs* a, hipStream_t s, int query);
 }

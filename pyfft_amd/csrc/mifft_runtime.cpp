@@ -177,14 +177,6 @@ int current_cus() {
 // grid cap of the grid-stride wave kernels: 8 work-groups of 4 waves per CU
 int wave_max_blocks() { return current_cus() * 8; }
 
-// The statically dealt sequential work list (lag == 0) is deadlock-free only while every work-group of the launch is resident:
-// the grid is capped at `per_cu` work-groups per compute unit (what the kernel's registers and LDS allow), whatever the caller asked for
-int resident_grid(int grid, int per_cu) {
-    const int cus = current_cus();
-    const int cap = per_cu * (cus > 0 ? cus : 1);
-    return grid > cap ? cap : grid;
-}
-
 long long wave_bytes(const mifft_pass* p, const mifft::TileArgs* a) {   // bytes of one side of a dense ROW pass
     return a->total * p->L * (p->precision == MIFFT_F64 ? 16ll : 8ll);
 }
@@ -496,6 +488,9 @@ bool mixed_rows_prefer_nd(bool f64, int n) {
     return f64 || n > 3200;
 }
 
+// keys 1, 4 and 11 are retired: they selected kernel forms this library no longer has (include/mifft.h)
+bool debug_key_ok(int key) { return key >= 0 && key < MIFFT_DEBUG_KEYS && key != 1 && key != 4 && key != 11; }
+
 // work-list control block of a persistent launch from the caller's mifft_fused_sync (include/mifft.h): validates, zeroes the
 // counters on `stream` when the caller does not alternate between two sets
 int fill_ctl(mifft::FusedCtl* c, const mifft_fused_sync* sync, long long outer, int lag, int ring_slots, unsigned tiles0, unsigned tiles1,
@@ -545,23 +540,15 @@ extern "C" {
 
 int mifft_abi_version(void) { return MIFFT_ABI_VERSION; }
 int mifft_debug_set(int32_t key, int32_t value) {
-    if (key < 0 || key >= MIFFT_DEBUG_KEYS) return set_err(MIFFT_E_INVALID, "bad debug key %d", key);
+    if (!debug_key_ok(key)) return set_err(MIFFT_E_INVALID, "bad debug key %d", key);
     t_debug_value[key] = value;
     t_debug_mask |= 1u << key;
     return 0;
 }
 int mifft_debug_set_default(int32_t key, int32_t value) {
-    if (key < 0 || key >= MIFFT_DEBUG_KEYS) return set_err(MIFFT_E_INVALID, "bad debug key %d", key);
+    if (!debug_key_ok(key)) return set_err(MIFFT_E_INVALID, "bad debug key %d", key);
     g_debug_default[key].store(value, std::memory_order_relaxed);
     return 0;
-}
-int mifft_has_feature(int32_t feature) {
-#ifdef MIFFT_DEV_BUILD
-    return (feature >= MIFFT_FEATURE_XCD2 && feature <= MIFFT_FEATURE_AB_FORMS) ? 1 : 0;
-#else
-    (void)feature;
-    return 0;
-#endif
 }
 int mifft_debug_get(int32_t key) { return (key >= 0 && key < MIFFT_DEBUG_KEYS) ? g_debug[key] : 0; }
 const char* mifft_last_error(void) { return g_err; }
@@ -938,11 +925,7 @@ int mifft_launch_fused2(const mifft_pass* p0, const mifft_pass* p1, const void* 
     if (!in0 || !out0 || !ring0 || (split && (!in1 || !out1))) return set_err(MIFFT_E_INVALID, "fused2: null buffer");
     (void)ring1;  // the ring is always interleaved
     if (grid < 1) return set_err(MIFFT_E_INVALID, "fused2: grid >= 1");
-    // lag == 0: the sequential list of a tiny batch, one ring slot per transform
-    if (lag == 0 && !mifft_has_feature(MIFFT_FEATURE_SEQUENTIAL_LIST))
-        return set_err(MIFFT_E_UNSUPPORTED, "fused2: the sequential list (lag == 0) is a development form, not in this build (make DEV=1)");
-    if (lag == 0 ? ring_slots != p1->outer && p1->outer > 0 : (ring_slots < 2 || lag < 1 || lag >= ring_slots))
-        return set_err(MIFFT_E_INVALID, "fused2: need 1 <= lag < ring_slots, or lag == 0 with ring_slots == outer");
+    if (ring_slots < 2 || lag < 1 || lag >= ring_slots) return set_err(MIFFT_E_INVALID, "fused2: need 1 <= lag < ring_slots");
     if (((uintptr_t)in0 | (uintptr_t)out0 | (uintptr_t)ring0 | (uintptr_t)in1 | (uintptr_t)out1) & 15)
         return set_err(MIFFT_E_INVALID, "data buffers must be 16-byte aligned");
     if (p1->outer == 0) return 0;
@@ -998,10 +981,6 @@ int mifft_launch_fused2(const mifft_pass* p0, const mifft_pass* p1, const void* 
     const bool wide2d = twod && !f64 && !split && !narrow && mifft_fused2dw_f32(p1->L, p0->L, nullptr, 0, nullptr, 1, &tiles0, &tiles1) == 0;
     rc = fill_ctl(&f.c, sync, p1->outer, lag, ring_slots, tiles0, tiles1, (hipStream_t)stream, "fused2");
     if (rc) return rc;
-    if (lag == 0) {
-        const bool wide = (f64 && (p0->L > 512 || p1->L > 512)) || p0->L == 2048 || p1->L == 2048 || siblings;       // 512- / 1024-thread tiles: one work-group per CU
-        grid = resident_grid(grid, wide ? 1 : 2);
-    }
     rc = rowfirst ? mifft_fused2r_f32(p1->L, p0->L, &f, (unsigned)grid, (hipStream_t)stream, 0) :
          wide2d ? mifft_fused2dw_f32(p1->L, p0->L, &f, (unsigned)grid, (hipStream_t)stream, 0, nullptr, nullptr) :
          wide32 ? mifft_fused2w_f32_launch(p0->L, p1->L, &f, (unsigned)grid, (hipStream_t)stream) :
@@ -1010,41 +989,6 @@ int mifft_launch_fused2(const mifft_pass* p0, const mifft_pass* p1, const void* 
        : f64 ? mifft_fused3_f64_launch(p0->L, p1->L, &f, split ? 1 : 0, (unsigned)grid, (hipStream_t)stream)
              : mifft_fused2_f32_launch(p0->L, p1->L, &f, split ? 1 : 0, (unsigned)grid, (hipStream_t)stream);
     if (rc == MIFFT_E_UNSUPPORTED) return set_err(rc, "fused2: no kernel for %d x %d", p0->L, p1->L);
-    if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
-    return 0;
-}
-
-int mifft_launch_fused2x(const mifft_pass* p0, const mifft_pass* p1, const void* in0, const void* in1, void* out0, void* out1, void* ring0,
-                         int32_t ring_slots, int32_t lag, const mifft_fused_sync* sync, int32_t grid, mifft_stream_t stream) {
-    if (!mifft_has_feature(MIFFT_FEATURE_FUSED2X))
-        return set_err(MIFFT_E_UNSUPPORTED, "fused2x: a development strategy, not in this build of the library (make DEV=1; mifft_has_feature)");
-    int rc = validate(p0);
-    if (rc) return rc;
-    rc = validate(p1);
-    if (rc) return rc;
-    if (p0->precision != MIFFT_F32 || p1->precision != MIFFT_F32 || p0->layout != p1->layout)
-        return set_err(MIFFT_E_UNSUPPORTED, "fused2x: fp32 only, one layout on both sides");
-    const bool split = p0->layout == MIFFT_SPLIT;
-    if (p0->kind != MIFFT_PASS_COL || p1->kind != MIFFT_PASS_COL || p0->S != 1 || p0->M != p1->L || p1->M != 1 ||
-        p1->S != p0->L || p0->outer != p1->outer || p0->inverse != p1->inverse)
-        return set_err(MIFFT_E_INVALID, "fused2x: passes are not the two passes of one long contiguous axis");
-    if (!in0 || !out0 || !ring0 || (split && (!in1 || !out1))) return set_err(MIFFT_E_INVALID, "fused2x: null buffer");
-    if (ring_slots < 2 || lag < 1 || lag >= ring_slots || grid < 1) return set_err(MIFFT_E_INVALID, "fused2x: need 1 <= lag < ring_slots, grid >= 1");
-    if (((uintptr_t)in0 | (uintptr_t)out0 | (uintptr_t)ring0 | (uintptr_t)in1 | (uintptr_t)out1) & 15)
-        return set_err(MIFFT_E_INVALID, "data buffers must be 16-byte aligned");
-    if (p1->outer == 0) return 0;
-    const int64_t n = (int64_t)p0->L * p1->L;
-    mifft::FusedArgs f;
-    fill_args(p0, in0, in1, ring0, nullptr, &f.p0);
-    fill_args(p1, ring0, nullptr, out0, out1, &f.p1);
-    f.p0.ostride_out = n;
-    f.p1.ostride_in = n;
-    f.p0.split_out = 0;      // the ring is interleaved for both layouts
-    f.p1.split = 0;
-    rc = fill_ctl(&f.c, sync, p1->outer, lag, ring_slots, (unsigned)(p0->M / 16), (unsigned)(p1->S / 16), (hipStream_t)stream, "fused2x");
-    if (rc) return rc;
-    rc = mifft_fused2x_f32_launch(p0->L, p1->L, &f, split ? 1 : 0, (unsigned)grid, (hipStream_t)stream);
-    if (rc == MIFFT_E_UNSUPPORTED) return set_err(rc, "fused2x: no kernel for %d x %d", p0->L, p1->L);
     if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
     return 0;
 }
@@ -1087,10 +1031,7 @@ int mifft_launch_fused_pair(const mifft_pass* passes, const void* in0, const voi
     if (ring0 == in0 || ring0 == out0) return set_err(MIFFT_E_INVALID, "fused pair: the ring must be a buffer of its own");
     if (grid < 1) return set_err(MIFFT_E_INVALID, "fused pair: grid >= 1");
     const long long batch = pz->outer;
-    if (lag == 0 && !mifft_has_feature(MIFFT_FEATURE_SEQUENTIAL_LIST))
-        return set_err(MIFFT_E_UNSUPPORTED, "fused pair: the sequential list (lag == 0) is a development form, not in this build (make DEV=1)");
-    if (lag == 0 ? ring_slots != batch && batch > 0 : (ring_slots < 2 || lag < 1 || lag >= ring_slots))
-        return set_err(MIFFT_E_INVALID, "fused pair: need 1 <= lag < ring_slots, or lag == 0 with ring_slots == outer");
+    if (ring_slots < 2 || lag < 1 || lag >= ring_slots) return set_err(MIFFT_E_INVALID, "fused pair: need 1 <= lag < ring_slots");
     if (batch == 0) return 0;
     mifft::FusedPairArgs f;
     memset(&f, 0, sizeof(f));
@@ -1114,62 +1055,9 @@ int mifft_launch_fused_pair(const mifft_pass* passes, const void* in0, const voi
     f.a1.scale = py1->scale * pz->scale;
     int rc = fill_ctl(&f.c, sync, batch, lag, ring_slots, tiles0, tiles1, (hipStream_t)stream, "fused pair");
     if (rc) return rc;
-    if (lag == 0) grid = resident_grid(grid, 2);
     rc = mifft_fusedp(f64, split ? 1 : 0, nx, ny, nz, &f, (unsigned)grid, (hipStream_t)stream, 0, nullptr, nullptr, nullptr);
     if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
     return 0;
-}
-
-int mifft_launch_xcd2(const mifft_pass* p0, const mifft_pass* p1, const void* in0, const void* in1, void* out0, void* out1,
-                      void* scratch, void* control, int32_t flags, mifft_stream_t stream) {
-#ifndef MIFFT_DEV_BUILD
-    (void)p0; (void)p1; (void)in0; (void)in1; (void)out0; (void)out1; (void)scratch; (void)control; (void)flags; (void)stream;
-    return set_err(MIFFT_E_UNSUPPORTED, "xcd2: a development strategy, not in this build of the library (make DEV=1; mifft_has_feature)");
-#else
-    int rc = validate(p0);
-    if (rc) return rc;
-    rc = validate(p1);
-    if (rc) return rc;
-    if (p0->precision != MIFFT_F32 || p1->precision != MIFFT_F32) return set_err(MIFFT_E_UNSUPPORTED, "xcd2: fp32 only");
-    if (p0->kind != MIFFT_PASS_COL || p1->kind != MIFFT_PASS_COL || p0->S != 1 || p0->M != p1->L || p1->M != 1 ||
-        p1->S != p0->L || p0->outer != p1->outer || p0->layout != p1->layout || p0->inverse != p1->inverse)
-        return set_err(MIFFT_E_INVALID, "xcd2: passes are not the two passes of one long contiguous axis");
-    if (p0->L != 1024 || p1->L != 1024) return set_err(MIFFT_E_UNSUPPORTED, "xcd2: no kernel for %d x %d", p0->L, p1->L);
-    const bool split = p0->layout == MIFFT_SPLIT;
-    if ((p0->flags & MIFFT_FLAG_SRC_INTERLEAVED) || (p1->flags & MIFFT_FLAG_DST_INTERLEAVED))
-        return set_err(MIFFT_E_INVALID, "xcd2: the user sides follow the plan layout");
-    if (!in0 || !out0 || !scratch || !control || (split && (!in1 || !out1))) return set_err(MIFFT_E_INVALID, "xcd2: null buffer");
-    if (((uintptr_t)in0 | (uintptr_t)out0 | (uintptr_t)in1 | (uintptr_t)out1) & 15)
-        return set_err(MIFFT_E_INVALID, "data buffers must be 16-byte aligned");
-    if ((uintptr_t)scratch & 255) return set_err(MIFFT_E_INVALID, "xcd2: scratch must be 256-byte aligned");
-    // in place is fine: every point of a transform is in registers before any of its output is stored
-    if (p0->outer == 0) return 0;
-    if (p0->outer > 0x0fffffff) return set_err(MIFFT_E_INVALID, "xcd2: batch too large");
-    int dev = 0;
-    rc = hip_check(hipGetDevice(&dev), "hipGetDevice");
-    if (rc) return rc;
-    int cus = 0;
-    rc = hip_check(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev), "hipDeviceGetAttribute");
-    if (rc) return rc;
-    if (cus != 256) return set_err(MIFFT_E_UNSUPPORTED, "xcd2: needs 8 XCDs x 32 CUs (device has %d CUs)", cus);
-    mifft::Xcd2Args f;
-    fill_args(p0, in0, in1, nullptr, nullptr, &f.p0);
-    fill_args(p1, nullptr, nullptr, out0, out1, &f.p1);
-    f.ctl = (unsigned*)control;
-    f.scratch = scratch;
-    f.batch = (unsigned)p0->outer;
-    // development trace (MIFFT_XCD2_TRACE): 32 time stamps per work-group behind the control words
-    f.trace = (flags & MIFFT_XCD2_TRACE) ? (unsigned long long*)((char*)control + MIFFT_XCD2_CONTROL_BYTES) : nullptr;
-    f.trace_iter = (unsigned)((flags >> 8) & 0xffff);   // (flags bits 4..6: elimination mode, development)
-    f.pace = (flags & 4) ? 1u : 0u;
-    f.phase_us = (unsigned)((flags >> 24) & 0x7f);       // (flags bits 24..30: start offset of the odd XCDs in microseconds, development)
-    rc = hip_check(hipMemsetAsync(control, 0, MIFFT_XCD2_CONTROL_BYTES, (hipStream_t)stream), "hipMemsetAsync");
-    if (rc) return rc;
-    rc = mifft_xcd2_f32_launch(&f, split ? 1 : 0, (flags & MIFFT_XCD2_PREFETCH) ? 1 : 0, (flags >> 4) & 7, 2u * (unsigned)cus, (hipStream_t)stream);
-    if (rc == MIFFT_E_UNSUPPORTED) return set_err(rc, "xcd2: elimination modes exist for the interleaved prefetching form only");
-    if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
-    return 0;
-#endif
 }
 
 int mifft_launch_chain_pipelined(const mifft_pass* passes, int32_t npasses, void* const bufs0[3], void* const bufs1[3],

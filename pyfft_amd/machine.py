@@ -89,10 +89,5 @@ class Machine(object):
             lag = max(1, rr["capped_lag"][0] * ring // rr["capped_lag"][1])
         return lag, ring, grid
 
-    @property
-    def xcd_cooperative(self):
-        """The XCD-cooperative kernels (xcd2; per-XCD work lists) assume 8 XCDs of 32 CUs."""
-        return self.num_xcc == 8 and self.compute_units == 32 * self.num_xcc
-
     def __repr__(self):
         return "Machine(cus=%d, xcc=%d, l2=%d KiB, llc=%d MiB)" % (self.compute_units, self.num_xcc, self.l2_bytes >> 10, self.llc_bytes >> 20)

@@ -126,8 +126,6 @@ class FFTPlan(object):
         self._counter_set = 0
         self._counters_clean = False
         self._errword = None         # pinned host word the persistent kernels report a dependency time-out in
-        self._xcd2_scratch = None
-        self._xcd2_disabled = False
         self._mailbox = None
         self._last_call_key = None
         self._last_call = None
@@ -313,10 +311,9 @@ class FFTPlan(object):
     #   pipelined  batch cut into cache-sized chunks, chunk i on side stream i % n with its own temp slot
     #              (mifft_launch_chain_pipelined)
     #   fused2     both passes of a long 1-D transform / a big 2-D one in one persistent launch (mifft_launch_fused2)
-    #   fused2x    the same with one work list per XCD (mifft_launch_fused2x): on request (2^17 on 16-column tiles: + 2 points)
     #   fusedp     both pass PAIRS of a cache-sized 3-D cube in one persistent launch (mifft_launch_fused_pair)
-    #   xcd2       1024 x 1024 fp32: one persistent launch, each transform stays on one XCD between its two HBM
-    #              crossings (mifft_launch_xcd2); development only
+    # (the per-XCD work lists, the XCD-resident single-crossing kernel and the sequential list of tiny batches were measured and not
+    # adopted: docs/negative_results.md)
     # Every size below comes from the device (pyfft_amd/machine.py: fractions of the last-level cache, multiples of the CU count).
     # ---- which persistent launch, if any: the plan's SHAPE CLASS matched against the rules of the tuning table -----------------
     def _shape_class(self):
@@ -401,43 +398,6 @@ class FFTPlan(object):
         big = item_bytes >= int(rule.get("min_item_bytes", 0)) or forced == "fused"
         return ("fused2z" if planes > 1 else name, lag, ring, grid) if (batch >= 2 * ring and big) else None
 
-    def _development_strategy(self, batch, forced, tiny):
-        """The measured-and-not-adopted forms, on request (PYFFT_AMD_* switches; `make DEV=1` builds of the library): the sequential
-        list of a tiny batch, the per-XCD work lists, the XCD-resident single-crossing kernel.  docs/strategies.md."""
-        p = self._params
-        mach = self._context.machine
-        dev = mach.tuning.development
-        rule = self._persistent_rule()
-        item_bytes = p.size * p.complex_nbytes
-        if tiny:
-            if D.small_fused(int(dev["small_fused_lag_div"])) and N.lib.mifft_has_feature(N.FEATURE_SEQUENTIAL_LIST) == 1 and \
-                    not p.split and rule is not None and not rule.get("on_request") and not self._plane_fused():
-                # statically dealt list: every work-group must be resident (1 or 2 per CU by the kernels' resources)
-                return (rule["strategy"], 0, batch, int(rule["per_cu"]) * mach.compute_units)
-            return None
-        one_d = rule is not None and rule["kind"] == "1d" and p.precision == N.F32
-        k = self._kernels
-        xcd_ok = one_d and k[0].L <= 1024 and k[0].L >= k[1].L and mach.xcd_cooperative
-        lists_ok = xcd_ok and N.lib.mifft_has_feature(N.FEATURE_FUSED2X) == 1
-        if forced == "fusedx" and lists_ok and batch >= 64:
-            lag, ring = D.fusedx()[:2]            # explicit lag / ring slots per XCD
-            return ("fused2x", lag, ring, 2 * mach.compute_units)
-        if forced == "xcd" and xcd_ok and k[0].L == 1024 and k[1].L == 1024 and not self._xcd2_disabled and \
-                N.lib.mifft_has_feature(N.FEATURE_XCD2) == 1 and batch >= int(dev["xcd2_min_batch"]):
-            return ("xcd2", D.xcd2_flags(N.XCD2_PREFETCH))
-        if forced == "auto" and lists_ok and not D.no_fusedx():
-            lag, ring = dev["fusedx_lag_ring"]
-            # 2^17 on the 16-column tiles (MIFFT_NARROW_TILES=1): + 2 points over the pipelined chunks (profiles/r04_d_list_sweep.log)
-            if k[0].L * k[1].L == (1 << 17) and N.lib.mifft_debug_get(N.DEBUG_NARROW_TILES) == 1 and \
-                    batch >= 8 * 2 * ring and 8 * ring * item_bytes <= mach.ring_bytes:
-                return ("fused2x", lag, ring, 2 * mach.compute_units)
-            # split-complex planes with PYFFT_AMD_SPLIT_FUSEDX: sibling tiles share an XCD's L2 (profiles/r04_ac_split_siblings.log)
-            if p.split and D.split_fusedx():
-                ring = min(ring, (mach.ring_bytes * 4 // 7) // (8 * item_bytes))
-                if ring >= 6 and batch >= 8 * 2 * ring:
-                    return ("fused2x", ring // 2, ring, 2 * mach.compute_units)
-        return None
-
     def _select_strategy(self, batch):
         """How the batch is cut and overlapped (docs/strategies.md).  Every measured constant comes from the tuning table
         (pyfft_amd/tuning_gfx950.json) and every size from the device (pyfft_amd/machine.py)."""
@@ -448,11 +408,8 @@ class FFTPlan(object):
         target = D.pipeline_chunk_bytes(mach.pipeline_chunk_bytes)
         # up to the cache size per side one launch per pass over the whole batch is the fastest form: the fork / join of the chunks and
         # the fill / drain of the persistent kernels only pay beyond it (profiles/r03_d_pipeline_threshold.log)
-        tiny = forced == "auto" and batch * item_bytes <= mach.chain_max_bytes
-        small = tiny or target < 1
-        strat = self._development_strategy(batch, forced, tiny) if (tiny or not small) else None
-        if strat is None and not small:
-            strat = self._persistent_strategy(batch, forced)
+        small = (forced == "auto" and batch * item_bytes <= mach.chain_max_bytes) or target < 1
+        strat = None if small else self._persistent_strategy(batch, forced)
         if strat is not None:
             return strat
         # any multi-pass plan gains from cache-sized chunks (the second pass re-reads what the first just wrote)
@@ -467,7 +424,7 @@ class FFTPlan(object):
             return ("pipelined", chunk, D.pipeline_streams(pipe["streams"]), nslab)
         return ("chain",)
 
-    PERSISTENT = ("fused2", "fused2x", "fusedp", "fused2z")
+    PERSISTENT = ("fused2", "fusedp", "fused2z")
 
     def _prepare(self, batch):
         """Choose the strategy when the batch changes (plan.py:179-192); the plan-owned scratch of that strategy is allocated by the
@@ -486,12 +443,12 @@ class FFTPlan(object):
         side streams): once an execute() has been recorded into a graph, scratch that is about to be replaced or released moves to
         a keep-alive list instead of being freed, so that later replays of that graph still find it (hip.Graph docstring)."""
         if self._captured:
-            held = (self._tempmemobj, self._counters, self._errword, self._xcd2_scratch, self._side_streams, self._side_events)
+            held = (self._tempmemobj, self._counters, self._errword, self._side_streams, self._side_events)
             if any(h is not None for h in held) and not any(k is held or k == held for k in self._capture_keepalive):
                 self._capture_keepalive.append(held)
 
     def _scratch_needed(self):
-        return self._strategy[0] == "xcd2" or self._temp_buffer_needed or self._strategy[0] in self.PERSISTENT or \
+        return self._temp_buffer_needed or self._strategy[0] in self.PERSISTENT or \
             (self._strategy[0] == "pipelined" and self._side_streams is None)
 
     def _ensure_scratch(self):
@@ -510,16 +467,10 @@ class FFTPlan(object):
             from .hip import Stream, Event
             self._side_streams = [Stream() for _ in range(self._strategy[2])]
             self._side_events = [Event() for _ in range(self._strategy[2] + 1)]
-        if self._strategy[0] == "xcd2":
-            if self._xcd2_scratch is None:
-                self._xcd2_scratch = ctx.allocate_raw(N.XCD2_SCRATCH_BYTES)
-            self._counters = ctx.allocate_raw(N.XCD2_CONTROL_BYTES + N.XCD2_TRACE_BYTES)
-            return
         if not self._temp_buffer_needed and self._strategy[0] not in self.PERSISTENT:
             return
         if self._strategy[0] in self.PERSISTENT:
-            # ring slots: `ring` of them; the per-XCD lists hold `ring` slots for each of the 8 XCDs
-            items = self._strategy[2] * (8 if self._strategy[0] == "fused2x" else 1)
+            items = self._strategy[2]       # ring slots
             # two counter sets: every launch runs on one and zeroes the other (mifft_fused_sync), so no memset precedes a launch;
             # a third one for launches captured into a graph (_fused_sync)
             planes = int(p.z) if self._strategy[0] == "fused2z" else 1
@@ -575,27 +526,10 @@ class FFTPlan(object):
             return
         descs = self._descriptors(batch, is_inplace, bool(inverse))
         strat = self._strategy
-        if strat[0] == "xcd2":
-            if capturing:
-                raise RuntimeError("pyfft_amd: the development strategy xcd2 cannot be captured into a graph")
-            d0, d1 = descs[0], descs[1]
-            in1 = bufs1[d0.src] if bufs1 is not None else None
-            out1 = bufs1[d1.dst] if bufs1 is not None else None
-            N.check(N.lib.mifft_launch_xcd2(ctypes.byref(d0), ctypes.byref(d1), bufs0[d0.src], in1, bufs0[d1.dst], out1,
-                                            ctx.pointer_of(self._xcd2_scratch), ctx.pointer_of(self._counters),
-                                            strat[1], stream), "mifft_launch_xcd2")
-            self._post_error_word(stream)
-        elif strat[0] in self.PERSISTENT:
+        if strat[0] in self.PERSISTENT:
             sync = self._fused_sync(stream, capturing)
             try:
-                if strat[0] == "fused2x":
-                    _, lag, ring, grid = strat
-                    d0, d1 = descs[0], descs[1]
-                    in1 = bufs1[d0.src] if bufs1 is not None else None
-                    out1 = bufs1[d1.dst] if bufs1 is not None else None
-                    N.check(N.lib.mifft_launch_fused2x(ctypes.byref(d0), ctypes.byref(d1), bufs0[d0.src], in1, bufs0[d1.dst], out1, bufs0[2],
-                                                       ring, lag, ctypes.byref(sync), grid, stream), "mifft_launch_fused2x")
-                elif strat[0] == "fusedp":
+                if strat[0] == "fusedp":
                     _, lag, ring, grid = strat
                     if self._pair_alt is not None:       # the four-pass list of this launch alone (the chain is plane pass + z pass)
                         descs = self._descriptors(batch, is_inplace, bool(inverse), alt=True)
@@ -647,16 +581,9 @@ class FFTPlan(object):
             N.check(N.lib.mifft_launch_chain(descs, len(self._kernels), bufs0, bufs1, stream), "mifft_launch_chain")
 
     # ---- error reporting of the persistent kernels --------------------------------------------------------------------
-    # fused2 / fused2x / fusedp write a PINNED HOST word (hip.ErrorWord) when a bounded dependency wait times out; the host looks
-    # at it on entry of every execute() (check(), never blocks) and after synchronising (finish()): an asynchronous caller learns
-    # of invalid results at its next call at the latest.  The development strategy xcd2 keeps rounds 2-3's mechanism: word [1] of
-    # its control block copied into pinned memory behind every launch (hip.ErrorMailbox).
-    def _post_error_word(self, stream):
-        if self._mailbox is None:
-            from .hip import ErrorMailbox
-            self._mailbox = ErrorMailbox()
-        self._mailbox.post(self._context.pointer_of(self._counters) + 4, stream, self._strategy[0])
-
+    # fused2 / fusedp write a PINNED HOST word (hip.ErrorWord) when a bounded dependency wait times out; the host looks at it on entry
+    # of every execute() (check(), never blocks) and after synchronising (finish()): an asynchronous caller learns of invalid results at
+    # its next call at the latest.  hip.ErrorMailbox (words copied into pinned memory behind a launch) is collected here as well.
     def _take_error_word(self):
         if self._errword is not None:
             word = self._errword.take()
@@ -681,13 +608,6 @@ class FFTPlan(object):
 
     def _handle_errors(self, errors):
         for strategy, word in errors:
-            if strategy == "xcd2" and (word & 2):
-                # the launch did not find 64 resident work-groups per XCD (the device is shared): nothing was written;
-                # this plan stops using the strategy
-                self._xcd2_disabled = True
-                self._last_batch_size = 0
-                raise RuntimeError("pyfft_amd: XCD-cooperative launch found no full XCD residency; results of that execute() "
-                                   "are invalid -- the plan has switched strategy, run it again")
             raise RuntimeError("pyfft_amd: %s kernel dependency time-out (results invalid)" % strategy)
 
     def _buffers(self, is_inplace, args):
@@ -799,7 +719,6 @@ class FFTPlan(object):
             self._scratch_ready = False
             self._tempmemobj = None
             self._counters = None
-            self._xcd2_scratch = None
             self._side_streams = None
             self._side_events = None
             self._mailbox = None

@@ -24,7 +24,6 @@ class Tuning(object):
         self.fractions = {k: (int(v[0]), int(v[1])) for k, v in table["cache_fractions"].items() if isinstance(v, list)}
         self.ring_rule = table["ring_rule"]
         self.pipelined = table["pipelined"]
-        self.development = table["development"]
         self.rules = list(table["rules"])
         # one-launch N-D shapes that run the run-time-shaped kernel: {precision: (always, big)} as sets of (x, y, z)
         ng = table.get("nd_generic", {})

@@ -2,8 +2,8 @@
 -- every shape of profiles/r04_long_1d_sizes.log / r04_second_batch_shapes.log / r04_t_tail_survey.log at several buffer sizes, on the
 full part, a one-XCD partition and a device without a last-level cache.  Written with the planner of commit 2d3a19f (end of round 4),
 BEFORE its thresholds moved into pyfft_amd/tuning_gfx950.json: tests/test_host.py::test_strategy_snapshot keeps the table-driven
-planner on the same answers.  Written against a `make DEV=1` build of the library (the per-XCD work lists appear under
-MIFFT_NARROW_TILES=1; the test skips those rows on the default build).  Runs without a GPU (the library's support queries need none):
+planner on the same answers.  Written against a library that still had the per-XCD work lists (they appear under
+MIFFT_NARROW_TILES=1; the strategy was retired since and the test skips those 18 rows).  Runs without a GPU (the library's support queries need none):
 
     python tests/golden/make_strategy_snapshot.py            # rewrites the json
 """

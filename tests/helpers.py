@@ -4,11 +4,6 @@ HipContext mirrors helpers.CudaContext (test/helpers.py:29-74): allocate / toGpu
 getPlan / timers / supportsDouble.  Data generation and the error metric come from the oracle
 (oracle/pyfft_oracle.py), which only tests may import.
 """
-import os
-import re
-import subprocess
-import sys
-
 import numpy
 
 COMPLEX_DTYPES = [numpy.complex64, numpy.complex128]
@@ -65,20 +60,6 @@ class CountingPool(object):
     def allocate(self, nbytes):
         self.calls += 1
         return self.hip.DeviceAllocation(nbytes)
-
-
-def run_on_dev_build(nodeid):
-    """Run the test `nodeid` in a child pytest process on the `make DEV=1` library (PYFFT_AMD_DEV_BUILD=1: pyfft_amd/_native.py loads
-    pyfft_amd/libmifft_dev.so, which __graft_entry__.build() makes next to the default one) and fail unless it passes there.  For the
-    tests of the development strategies, whose launchers the default library does not contain."""
-    assert not os.environ.get("PYFFT_AMD_DEV_BUILD"), "the development library lacks the feature this test needs"
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, PYFFT_AMD_DEV_BUILD="1")
-    cmd = [sys.executable] + (["-s"] if sys.flags.no_user_site else []) + ["-m", "pytest", "-q", "-rs", "-p", "no:cacheprovider", nodeid]
-    out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
-    tail = (out.stdout[-3000:], out.stderr[-2000:])
-    summary = out.stdout.strip().splitlines()[-1] if out.stdout.strip() else ""
-    assert out.returncode == 0 and re.search(r"\b1 passed\b", summary) and "skipped" not in summary, tail
 
 
 def getDimensions(shape):

@@ -216,9 +216,9 @@ def keys_of_plan(plan, batch, mode="auto"):
     return keys
 
 
-# pair kernels of the library that only a development switch selects (MIFFT_DEBUG_PAIR = 2: the other y split of 256^3, interleaved fp64);
-# tests/test_pairs_gpu.py::test_pass_pairs_256_cubed_alternative_split runs it
-DEV_ONLY_PAIR_KEYS = {("pairXY", "f64", "interleaved", 256, 64, 4), ("pairYZ", "f64", "interleaved", 16384, 4, 256)}
+# pair kernels of the library that no default plan selects, only a development switch (MIFFT_DEBUG_PAIR = 2: the other y split of 256^3,
+# interleaved fp64); tests/test_pairs_gpu.py::test_pass_pairs_256_cubed_alternative_split runs it
+SWITCH_ONLY_PAIR_KEYS = {("pairXY", "f64", "interleaved", 256, 64, 4), ("pairYZ", "f64", "interleaved", 16384, 4, 256)}
 
 MAX_LOG2_POINTS = 24          # shapes of up to 2^24 points: 4096 x 4096, 256^3, 2^24 (128 MiB fp32 / 256 MiB fp64 per transform)
 
@@ -269,7 +269,7 @@ _audit = {}
 
 
 def audit_cases(max_log=MAX_LOG2_POINTS):
-    """[(shape, dtype name, batch, keys)]: for every key of universe() but DEV_ONLY_PAIR_KEYS, the smallest case (bytes per side) that
+    """[(shape, dtype name, batch, keys)]: for every key of universe() but SWITCH_ONLY_PAIR_KEYS, the smallest case (bytes per side) that
     selects it with batch >= 3, in a batch that is no multiple of 4 where the key allows one (tiles that hold several transforms then end
     partially filled); a case that is the smallest for several keys appears once, `keys` sorted.  Per (shape, dtype) the planner is asked
     at batch 3 and at universe()'s batches; a key that only appears at a larger batch is bisected down to the batch where it appears.
@@ -277,7 +277,7 @@ def audit_cases(max_log=MAX_LOG2_POINTS):
     if max_log in _audit:
         return list(_audit[max_log])
     uni = universe(max_log)
-    want = set(uni) - DEV_ONLY_PAIR_KEYS
+    want = set(uni) - SWITCH_ONLY_PAIR_KEYS
     best = {}                       # key -> (bytes, order, shape, dtype, batch)
     order = 0
     for shape in _shapes(max_log):
@@ -367,7 +367,7 @@ def _split(dt):
 
 
 # adapter(params) -> [(shape, dtype, batch, mode)]; None = the test builds no default power-of-two plan worth counting (API checks,
-# direct C-ABI launches, opt-in extensions, development strategies of `make DEV=1` builds)
+# direct C-ABI launches, opt-in extensions)
 REGISTRY = {
     "test_errors_gpu": {
         "test_errors_batch_1_and_3": lambda p: [_c(p["shape"], p["dtype"], b) for b in (1, 3) if _prod(p["shape"]) * b <= (1 << 19)],
@@ -418,23 +418,20 @@ REGISTRY = {
     },
     "test_persistent_gpu": {
         "test_async_error_mailbox": lambda p: [_c((1 << 20,), C64, 64)],
-        "test_xcd2_strategy_bit_identical_and_in_place": None,
         "test_error_mailbox_keeps_the_oldest_word_when_the_ring_is_full": None,
         "test_fused_pair_cube_128": lambda p: [_c((128, 128, 128), p["dtype"], p["batch"], "fused"), _c((128, 128, 128), p["dtype"], p["batch"], "chain")],
-        "test_per_xcd_lists": None,
         "test_fused_ring_rule_2_19": lambda p: [_c((1 << 19,), C64, 130), _c((1 << 19,), C64, 130, "chain")],
-        "test_sequential_single_launch_of_tiny_batches": None,
         "test_alternating_counter_sets_and_memset_form_agree": lambda p: [_c((1 << 20,), C64, 70)],
         "test_fused_2d_rectangles": lambda p: [_c(p["shape"], C64, p["batch"], "fused" if tuple(p["shape"]) == (512, 2048) else "auto"),
                                                _c(p["shape"], C64, p["batch"], "chain")],
         "test_fused_long_fp64": lambda p: [_c((p["n"],), C128, p["batch"], "fused"), _c((p["n"],), C128, p["batch"], "chain")],
         "test_fused_mid_sizes_fp64": lambda p: [_c((p["n"],), C128, p["batch"], "fused"), _c((p["n"],), C128, p["batch"], "chain")],
         "test_fused_2d_fp64_512_sides": lambda p: [_c(p["shape"], C128, p["batch"], "fused"), _c(p["shape"], C128, p["batch"], "chain")],
-        "test_wide_tiles_fp32_mid_sizes": lambda p: [_c((p["n"],), C64, p["batch"]), _c((p["n"],), C64, p["batch"], "chain")],
+        "test_wide_tiles_fp32_mid_sizes_against_the_chain": lambda p: [_c((p["n"],), C64, p["batch"]), _c((p["n"],), C64, p["batch"], "chain")],
         "test_fused_2d_256_sides": lambda p: ([] if (_is_double(p["dtype"]) and max(p["shape"]) > 512) else
                                               [_c(p["shape"], p["dtype"], p["batch"] // 2 + 1 if _is_double(p["dtype"]) else p["batch"]),
                                                _c(p["shape"], p["dtype"], p["batch"], "chain")]),
-        "test_split_planes_on_per_xcd_lists": lambda p: [_c((p["n"],), F32, p["batch"]), _c((p["n"],), F32, p["batch"], "chain")],
+        "test_split_planes_on_sibling_tiles": lambda p: [_c((p["n"],), F32, p["batch"]), _c((p["n"],), F32, p["batch"], "chain")],
         "test_fused_pair_small_axes": lambda p: [_c(p["shape"], p["dtype"], p["batch"] // 2 + 1 if _is_double(p["dtype"]) else p["batch"]),
                                                  _c(p["shape"], p["dtype"], p["batch"], "chain")],
         "test_fused_pair_split_planes": lambda p: [_c(p["shape"], p["rdtype"], p["batch"]), _c(p["shape"], p["rdtype"], p["batch"], "chain")],
@@ -449,7 +446,7 @@ REGISTRY = {
     },
     "test_pairs_gpu": {
         "test_pass_pairs_256_cubed": lambda p: [_c((256, 256, 256), p["dtype"], 1)],
-        "test_pass_pairs_256_cubed_alternative_split": None,         # (a development A/B instance: DEV_ONLY_PAIR_KEYS below)
+        "test_pass_pairs_256_cubed_alternative_split": None,         # (an A/B instance behind a development switch: SWITCH_ONLY_PAIR_KEYS above)
         "test_pair_chains_two_launches": lambda p: [_c(p["shape"], p["dtype"], p["batch"])],
         "test_pair_chains_pipelined_chunks": lambda p: [_c(p["shape"], p["dtype"], p["batch"])],
         "test_pass_pairs_for_256_point_rows": lambda p: [_c(p["shape"], p["dtype"], p["batch"])],
@@ -477,7 +474,7 @@ REGISTRY = {
         "test_perf_table_quick_uses_the_reference_formula": None,
         "test_plan_following_two_torch_streams_without_host_sync": lambda p: [_c((1 << 18,), C64, 160)],
         "test_plan_for_a_device_given_by_index": lambda p: [_c((4096,), C64, 4)],
-        "test_device_properties_describe_the_memory_system": None,
+        "test_device_props_carry_cus_xcds_and_caches": None,
         "test_plan_with_stream_and_context_index": lambda p: [_c((8192,), C64, 3)],
         "test_four_ranks_share_one_gpu": lambda p: [_c((1 << 20,), C64, 40)],
         "test_captured_execute_replays_bit_identically": lambda p: [_c(p["shape"], p["dtype"], p["batch"])],

@@ -476,17 +476,16 @@ def _strategy_on(machine, shape, dtype, batch):
     return plan, plan._select_strategy(batch)
 
 
-def test_planner_constants_come_from_the_device():
+def test_planner_constants_come_from_the_device_props():
     """On the full part (256 CUs, 8 XCDs, 256 MiB last-level cache) the machine model gives back the measured constants of
     rounds 1-3 and the round-4 ring rule; on a partition (32 CUs, one XCD, 32 MiB of cache) every ring, chunk and threshold
-    shrinks with the cache, the XCD-cooperative strategies disappear, and nothing is sized for a machine that is not there;
+    shrinks with the cache, and nothing is sized for a machine that is not there;
     without a last-level cache every plan is the plain chain (the reference's loop, pyfft/plan.py:217-248)."""
     import numpy
     from pyfft_amd.machine import Machine
     full = Machine(256, 8, 4 << 20, 256 << 20)
     assert (full.ring_bytes, full.pipeline_chunk_bytes, full.slab_bytes, full.chain_max_bytes, full.write_through_max_bytes) == \
         (224 << 20, 64 << 20, 128 << 20, 256 << 20, 128 << 20)
-    assert full.xcd_cooperative
     c64, c128 = numpy.complex64, numpy.complex128
     assert _strategy_on(full, (1 << 20,), c64, 4096)[1] == ("fused2", 14, 28, 512)            # BASELINE config 2, as in rounds 2-3
     assert _strategy_on(full, (1 << 19,), c64, 2048)[1] == ("fused2", 28, 56, 512)            # round 4: the ring fills the cache
@@ -512,7 +511,7 @@ def test_planner_constants_come_from_the_device():
     assert _strategy_on(full, (1 << 20,), c64, 32)[1] == ("chain",)                           # exactly the cache size per side
 
     part = Machine(32, 1, 4 << 20, 32 << 20)
-    assert not part.xcd_cooperative and part.ring_bytes == 28 << 20 and part.chain_max_bytes == 32 << 20
+    assert part.ring_bytes == 28 << 20 and part.chain_max_bytes == 32 << 20
     for shape, dtype, batch in (((1 << 20,), c64, 4096), ((1 << 19,), c64, 2048), ((1 << 18,), c64, 4096), ((1 << 17,), c64, 8192),
                                 ((1 << 22,), c64, 256), ((1024, 1024), c64, 512), ((128, 128, 128), c64, 64), ((256, 256, 256), c128, 8),
                                 ((1 << 20,), c128, 512), ((1024,), c64, 1 << 16)):
@@ -537,7 +536,7 @@ def test_planner_constants_come_from_the_device():
     assert full.fused_geometry(32 << 20, 128, 1) == (4, 7, 256)
 
 
-def test_round4_entry_points_reject_bad_arguments_without_touching_the_gpu():
+def test_persistent_entry_points_reject_bad_arguments_without_touching_the_gpu():
     """mifft_fused_sync validation and the fused pass-pair launcher (host side of the C ABI; every call returns before HIP)."""
     import ctypes
     from pyfft_amd import _native as N
@@ -562,18 +561,13 @@ def test_round4_entry_points_reject_bad_arguments_without_touching_the_gpu():
     # two alternating counter sets need an error word of their own (the next launch zeroes the default one, word 1 of line 0)
     assert N.lib.mifft_launch_fused2(byref(p0), byref(p1), 16, None, 32, None, 64, None, 28, 14, byref(N.MifftFusedSync(4096, 8192, None)), 512, None) == N.E_INVALID
     assert "error word of their own" in N.last_error(), N.last_error()
-    # the development forms (sequential list, per-XCD lists, XCD-resident kernel) exist in `make DEV=1` builds only; the default
-    # build says so loudly and mifft_has_feature tells beforehand
-    dev = [N.lib.mifft_has_feature(f) for f in (N.FEATURE_XCD2, N.FEATURE_FUSED2X, N.FEATURE_SEQUENTIAL_LIST)]
-    assert dev in ([0, 0, 0], [1, 1, 1]) and N.lib.mifft_has_feature(99) == 0
-    seq = N.lib.mifft_launch_fused2(byref(p0), byref(p1), 16, None, 32, None, 64, None, 28, 0, byref(ok), 512, None)    # sequential list: ring == outer
-    assert seq == (N.E_INVALID if dev[2] else N.E_UNSUPPORTED)
-    for sync in (None, byref(N.MifftFusedSync(4096, 4096, None))):
-        rc = N.lib.mifft_launch_fused2x(byref(p0), byref(p1), 16, None, 32, None, 64, 8, 4, sync, 512, None)
-        assert rc == (N.E_INVALID if dev[1] else N.E_UNSUPPORTED)
-    if not dev[0]:
-        assert N.lib.mifft_launch_xcd2(byref(p0), byref(p1), 16, None, 32, None, 256, 256, 1, None) == N.E_UNSUPPORTED
-        assert "DEV=1" in N.last_error()
+    # the measured-and-not-adopted forms are gone: lag == 0 (the sequential list of a tiny batch) is refused like any bad lag, and the
+    # per-XCD lists, the XCD-resident kernel and the feature query are no longer exported
+    assert N.lib.mifft_launch_fused2(byref(p0), byref(p1), 16, None, 32, None, 64, None, 28, 0, byref(ok), 512, None) == N.E_INVALID
+    assert "1 <= lag < ring_slots" in N.last_error(), N.last_error()
+    lib = ctypes.CDLL(N.LIB_PATH)
+    for name in ("mifft_has_feature", "mifft_launch_xcd2", "mifft_launch_fused2x"):
+        assert not hasattr(lib, name), name
     # the persistent pass-pair form exists for the shapes with every axis in {64, 128}, both precisions, both layouts
     I, S = N.INTERLEAVED, N.SPLIT
     assert N.lib.mifft_fused_pair_supported(N.F32, I, 128, 128, 128) == 0 and N.lib.mifft_fused_pair_supported(N.F64, I, 128, 128, 128) == 0
@@ -624,7 +618,7 @@ def test_pyfft_import_name():
         raise AssertionError("pyfft.cuda must not exist")
 
 
-def test_round5_debug_switches_are_per_thread_over_a_process_default():
+def test_debug_switches_are_per_thread_and_retired_keys_are_refused():
     """mifft_debug_set changes a development switch for the calling thread only; a thread that never set the key sees the process
     default (mifft_debug_set_default) -- a measurement in one thread cannot change the kernels of another thread's plan."""
     import threading
@@ -652,10 +646,14 @@ def test_round5_debug_switches_are_per_thread_over_a_process_default():
         N.lib.mifft_debug_set_default(key, 0)
         N.lib.mifft_debug_set(key, 0)
     assert seen == [("after the main thread's set", 0), ("after the default changed", 3)]
-    assert N.lib.mifft_debug_set(N.DEBUG_PREFETCH + 1, 1) == N.E_INVALID and N.lib.mifft_debug_set_default(-1, 1) == N.E_INVALID
+    assert N.lib.mifft_debug_set(N.DEBUG_KEYS, 1) == N.E_INVALID and N.lib.mifft_debug_set_default(-1, 1) == N.E_INVALID
+    # keys 1, 4 and 11 are retired (they selected forms the library no longer has): refused, and they read 0
+    for retired in (1, 4, 11):
+        assert N.lib.mifft_debug_set(retired, 1) == N.E_INVALID and N.lib.mifft_debug_set_default(retired, 1) == N.E_INVALID
+        assert N.lib.mifft_debug_get(retired) == 0
 
 
-def test_round5_capture_entry_points_reject_bad_arguments_without_touching_the_gpu():
+def test_capture_entry_points_reject_bad_arguments_without_touching_the_gpu():
     """Stream capture / graph replay shims (include/mifft.h): argument errors are negative library codes, never a crash."""
     import ctypes
     from pyfft_amd import _native as N
@@ -664,7 +662,7 @@ def test_round5_capture_entry_points_reject_bad_arguments_without_touching_the_g
     assert N.lib.mifft_stream_end_capture(None, None) == N.E_INVALID
     assert N.lib.mifft_graph_launch(None, None) == N.E_INVALID
     assert N.lib.mifft_graph_destroy(None) == 0
-    assert N.ABI_VERSION == 5 and N.lib.mifft_abi_version() == 5
+    assert N.ABI_VERSION == 6 and N.lib.mifft_abi_version() == 6
 
 
 def test_round5_no_split_rowfirst_follows_the_environment_into_the_library(monkeypatch):
@@ -680,7 +678,7 @@ def test_round5_no_split_rowfirst_follows_the_environment_into_the_library(monke
     assert D.no_split_rowfirst() is False and N.lib.mifft_debug_get(N.DEBUG_NO_ROWFIRST) == 0
 
 
-def test_strategy_snapshot_of_the_table_driven_planner():
+def test_strategy_snapshot_of_the_table_driven_planner_on_one_library():
     """FFTPlan._select_strategy is a lookup in pyfft_amd/tuning_gfx950.json since round 5.  It must answer what the round-4 planner
     (nested literals) answered for every shape of profiles/r04_long_1d_sizes.log / r04_second_batch_shapes.log / r04_t_tail_survey.log
     at seven buffer sizes on three devices, and on the full part under the development switches the choice depends on: tests/golden/strategy_snapshot.json.gz, written by make_strategy_snapshot.py BEFORE the move."""
@@ -694,8 +692,8 @@ def test_strategy_snapshot_of_the_table_driven_planner():
         want = json.load(f)
     got = snap.snapshot(with_chain_class=True)
     assert len(got) == len(want) > 30000
-    # (the per-XCD work lists are part of `make DEV=1` builds only: 18 rows of the 16-column A/B mode)
-    lists = N.lib.mifft_has_feature(N.FEATURE_FUSED2X) == 1
+    # (the golden file was written with the per-XCD work lists, a development strategy that is gone: its 18 rows of the 16-column
+    # A/B mode are not compared)
     # shapes whose CHAIN changed in round 5 (one pass pair instead of a third launch: (4096, 256), (32, 32, 2048) ...) no longer run
     # their leading passes slab-wise; they stay on the plain chain / the pipelined chunks
     new_chain = [g for g in got if g[6]]
@@ -709,9 +707,9 @@ def test_strategy_snapshot_of_the_table_driven_planner():
     cube32 = [g for w, g in zip(want, got) if tuple(g[2]) == (32, 32, 128) and g[5][0] == "fusedp"]
     assert cube32 and all(w[5][0] in ("chain", "pipelined") for w, g in zip(want, got) if tuple(g[2]) == (32, 32, 128) and g[5][0] == "fusedp")
     bad = [(w, g) for w, g in zip(want, got) if not g[6] and g[5][0] != "fused2z" and not (tuple(g[2]) == (32, 32, 128) and g[5][0] == "fusedp") and
-           w != json.loads(json.dumps(g[:6])) and (lists or w[5][0] != "fused2x")]
+           w != json.loads(json.dumps(g[:6])) and w[5][0] != "fused2x"]
     assert not bad, bad[:10]
-    assert not lists or sum(1 for g in got if g[5][0] == "fused2x") == 18
+    assert not any(g[5][0] == "fused2x" for g in got) and sum(1 for w in want if w[5][0] == "fused2x") == 18
     assert set(r[5][0] for r in want) == {"chain", "pipelined", "fused2", "fusedp", "fused2x"}
 
 

@@ -50,7 +50,7 @@ def test_pair_kernel_table_and_reachable_pair_keys_agree():
             plan = KC.plan_for(shape, numpy.dtype(dtname))
             chain = plan._pair_alt or plan._kernels
             fusedp_only |= KC._chain_keys(plan, chain)
-    dead = sorted(k for k in have - reached - fusedp_only - KC.DEV_ONLY_PAIR_KEYS)
+    dead = sorted(k for k in have - reached - fusedp_only - KC.SWITCH_ONLY_PAIR_KEYS)
     assert not dead, "pair kernels no default plan reaches: %r" % (dead,)
 
 

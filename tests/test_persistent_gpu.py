@@ -10,7 +10,7 @@ import numpy
 import pytest
 
 import pyfft_oracle as oracle
-from helpers import EPS_F, MAX_F, _execute, _execute_split, _noise, _test_data, run_on_dev_build
+from helpers import EPS_F, MAX_F, _execute, _execute_split, _noise, _test_data
 
 pytestmark = pytest.mark.gpu
 
@@ -48,52 +48,10 @@ def test_async_error_mailbox(ctx):
     plan.execute(a, b, batch=batch, wait_for_finish=True)                   # and the plan works again
     res = b.get().reshape(batch, n)
     assert numpy.allclose(res[:, 0], n) and numpy.abs(res[:, 1:]).max() < 1e-2
-    # the copy-back mailbox (development strategy xcd2) still turns a non-zero word into the same error
+    # the copy-back mailbox (hip.ErrorMailbox) turns a non-zero word into the same error
     plan._handle_errors([])
     with pytest.raises(RuntimeError):
         plan._handle_errors([("fused2", 1)])
-
-
-@pytest.mark.parametrize("dtype", [numpy.complex64, numpy.float32], ids=["interleaved", "split"])
-def test_xcd2_strategy_bit_identical_and_in_place(ctx, dtype, monkeypatch, request):
-    """The XCD-cooperative kernel (csrc/fft_xcd2.hpp, development strategy 'xcd'): bit-identical to the chain strategy,
-    forward and inverse, out of place and in place (it needs no temp buffer), and its error word stays clear.  The kernel is part
-    of `make DEV=1` builds of the library only (mifft_has_feature)."""
-    from pyfft_amd import _native as N
-    if N.lib.mifft_has_feature(N.FEATURE_XCD2) != 1:          # development strategy: not in the default build of libmifft.so
-        run_on_dev_build(request.node.nodeid)
-        return
-    n, batch = 1 << 20, 72
-    split = numpy.dtype(dtype).kind == "f"
-    rng = numpy.random.default_rng(77)
-    re = rng.standard_normal(n * batch).astype(numpy.float32)
-    im = rng.standard_normal(n * batch).astype(numpy.float32)
-    host = [re, im] if split else [(re + 1j * im).astype(numpy.complex64)]
-
-    def run(strategy, inverse, inplace):
-        monkeypatch.setenv("PYFFT_AMD_STRATEGY", strategy)
-        plan = ctx.getPlan((n,), dtype=dtype, context=ctx.context)
-        assert plan.strategy(batch)[0] == ("xcd2" if strategy == "xcd" else "chain")
-        src = [ctx.toGpu(h) for h in host]
-        dst = src if inplace else [ctx.allocate(h.shape, h.dtype) for h in host]
-        if inplace:
-            plan.execute(*src, inverse=inverse, batch=batch)
-        else:
-            plan.execute(*(src + dst), inverse=inverse, batch=batch)
-            for s_, h in zip(src, host):
-                assert numpy.array_equal(s_.get(), h)
-        return [d.get() for d in dst]
-
-    for inverse in (False, True):
-        want = run("chain", inverse, False)
-        for inplace in (False, True):
-            got = run("xcd", inverse, inplace)
-            for w, g in zip(want, got):
-                assert numpy.array_equal(w.view(numpy.uint32), g.view(numpy.uint32))
-    ref = numpy.fft.fft((re[:n].astype(numpy.float64) + 1j * im[:n]))
-    fw = run("xcd", False, False)
-    got = (fw[0][:n] + 1j * fw[1][:n]) if split else fw[0][:n]
-    assert numpy.abs(got - ref).max() <= 1e-5 * numpy.abs(ref).max()
 
 
 # ---- robustness --------------------------------------------------------------------------------------------------------
@@ -161,33 +119,6 @@ def test_fused_pair_cube_128(ctx, monkeypatch, dtype, batch):
     assert numpy.array_equal(b.get(), got)
 
 
-# ---- per-XCD work lists as a default ---------------------------------------------------------------------------------------
-@pytest.mark.parametrize("n,batch", [(1 << 16, 1040), (1 << 17, 520)], ids=str)
-def test_per_xcd_lists(ctx, monkeypatch, n, batch, request):
-    """The fused kernel with one work list per XCD (mifft_launch_fused2x; pyfft/kernel.py:259-283 chain semantics), on request
-    (within round 4 the 32-column tiles of the global list overtook it at 2^17): the bits of the chain, in place == out of place; a
-    batch that is not a multiple of 8 leaves the lists uneven, work stealing drains them."""
-    from pyfft_amd import _native as N
-    if N.lib.mifft_has_feature(N.FEATURE_FUSED2X) != 1:       # development strategy: not in the default build of libmifft.so
-        run_on_dev_build(request.node.nodeid)
-        return
-    if not ctx.hip.Machine.from_props(ctx.hip.device_props()).xcd_cooperative:
-        pytest.skip("needs 8 XCDs x 32 CUs")
-    data = _test_data((n,), numpy.complex64, batch, 91)
-    monkeypatch.setenv("PYFFT_AMD_STRATEGY", "chain")
-    want = _execute(ctx, (n,), numpy.complex64, batch, data, expect="chain")
-    monkeypatch.setenv("PYFFT_AMD_STRATEGY", "fusedx")
-    monkeypatch.setenv("PYFFT_AMD_FUSEDX", "8,16")
-    got = _execute(ctx, (n,), numpy.complex64, batch, data, expect="fused2x")
-    assert numpy.array_equal(want, got)
-    assert numpy.array_equal(_execute(ctx, (n,), numpy.complex64, batch, data, inplace=True, expect="fused2x"), got)
-    odd = batch - 3
-    got_odd = _execute(ctx, (n,), numpy.complex64, odd, data[:odd * n], expect="fused2x")
-    assert numpy.array_equal(got_odd, want[:odd * n])
-    monkeypatch.setenv("PYFFT_AMD_STRATEGY", "auto")
-    assert ctx.getPlan((n,), dtype=numpy.complex64).strategy(batch)[0] == "fused2"           # the plan's own choice: 32-column tiles
-
-
 def test_fused_ring_rule_2_19(ctx, monkeypatch):
     """2^19 = 1024 x 512 has 32 first-pass tiles per transform: the ring rule counts the lag in tiles (28 transforms, ring 56 =
     224 MiB), not in transforms (round 3: 14 / 28, four points lower) -- and the bits stay the chain's."""
@@ -200,42 +131,6 @@ def test_fused_ring_rule_2_19(ctx, monkeypatch):
     want = _execute(ctx, (n,), numpy.complex64, batch, data, expect="chain")
     monkeypatch.setenv("PYFFT_AMD_STRATEGY", "auto")
     assert numpy.array_equal(_execute(ctx, (n,), numpy.complex64, batch, data, expect="fused2"), want)
-
-
-# ---- tiny batches: the sequential work list (one launch instead of two) ------------------------------------------------------
-@pytest.mark.parametrize("shape,dtype,batch", [((1024, 1024), numpy.complex64, 4), ((1 << 20,), numpy.complex64, 3), ((1 << 18,), numpy.complex64, 7),
-                                               ((128, 128, 128), numpy.complex64, 2), ((128, 128, 128), numpy.complex128, 1),
-                                               ((1024, 1024), numpy.complex128, 2), ((1 << 22,), numpy.complex64, 1)],
-                         ids=lambda v: str(numpy.dtype(v).name) if isinstance(v, type) else str(v).replace(" ", ""))
-def test_sequential_single_launch_of_tiny_batches(ctx, monkeypatch, shape, dtype, batch, request):
-    """The reference's own benchmark protocol runs 32 MiB buffers (test/test_performance.py:11,22-30): there the two passes of a
-    transform are two dependent launches.  The sequential work list runs them in ONE persistent launch (lag 0: every first-pass
-    tile, then every second-pass tile); it must give the chain's bits, in place and out of place, forward and inverse.  Measured
-    slower than the two launches (docs/negative_results.md): part of `make DEV=1` builds of the library only."""
-    from pyfft_amd import _native as N
-    if N.lib.mifft_has_feature(N.FEATURE_SEQUENTIAL_LIST) != 1:   # development form: not in the default build of libmifft.so
-        run_on_dev_build(request.node.nodeid)
-        return
-    data = _test_data(shape, dtype, batch, 93)
-    monkeypatch.setenv("PYFFT_AMD_SMALL_FUSED", "0")
-    want = _execute(ctx, shape, dtype, batch, data, expect="chain")
-    monkeypatch.setenv("PYFFT_AMD_SMALL_FUSED", "1")
-    plan = ctx.getPlan(shape, dtype=dtype)
-    st = plan.strategy(batch)
-    assert st[0] in ("fused2", "fusedp") and st[1] == 0 and st[2] == batch, st
-    got = _execute(ctx, shape, dtype, batch, data)
-    if len(shape) == 2:
-        # the 2-D persistent form is two TRANSPOSING passes, the chain a ROW pass and a strided one: the same transform in another
-        # operation order (as in test_fused_2d_1024)
-        assert oracle.difference(want, got, batch) < (5e-7 if numpy.dtype(dtype) == numpy.complex64 else 1e-14)
-    else:
-        assert numpy.array_equal(want, got)
-    assert numpy.array_equal(_execute(ctx, shape, dtype, batch, data, inplace=True), got)
-    tol = 1.1e-6 if numpy.dtype(dtype) == numpy.complex64 else 1e-11
-    back = _execute(ctx, shape, dtype, batch, got, inverse=True)
-    assert oracle.difference(data, back, batch) < tol
-    ref = oracle.numpy_fft(numpy.fft.fftn, data, batch)
-    assert oracle.difference(ref, got, batch) < tol
 
 
 # ---- launches without memset / copy-back -----------------------------------------------------------------------------------
@@ -388,12 +283,11 @@ WIDE_TILE_CASES = [(1 << 16, 1040), (1 << 17, 530), (1 << 18, 161)] + ([(1 << 18
 
 
 @pytest.mark.parametrize("n,batch", WIDE_TILE_CASES, ids=str)
-def test_wide_tiles_fp32_mid_sizes(ctx, monkeypatch, n, batch):
+def test_wide_tiles_fp32_mid_sizes_against_the_chain(ctx, monkeypatch, n, batch):
     """fp32 N = 2^16 ... 2^18 in the persistent kernel on 32-column tiles (csrc/fft_col2w.hpp: a thread owns two adjacent columns,
-    16-byte lanes, 256-byte row segments) by the plan's own choice: the bits of the chain (same butterflies, same table factors) and
-    of the 16-column tiles, in place, numpy with the reference's thresholds, inverse round trip; a batch that fills the ring only
-    once takes half the pipeline instead of falling back to the chunks."""
-    N = ctx.hip.N
+    16-byte lanes, 256-byte row segments) by the plan's own choice: the bits of the chain (same butterflies, same table factors), in
+    place, numpy with the reference's thresholds, inverse round trip; a batch that fills the ring only once takes half the pipeline
+    instead of falling back to the chunks."""
     data = _test_data((n,), numpy.complex64, batch, 98)
     monkeypatch.setenv("PYFFT_AMD_STRATEGY", "chain")
     want = _execute(ctx, (n,), numpy.complex64, batch, data, expect="chain")
@@ -401,14 +295,6 @@ def test_wide_tiles_fp32_mid_sizes(ctx, monkeypatch, n, batch):
     got = _execute(ctx, (n,), numpy.complex64, batch, data, expect="fused2")
     assert numpy.array_equal(want, got)
     assert numpy.array_equal(_execute(ctx, (n,), numpy.complex64, batch, data, inplace=True, expect="fused2"), got)
-    if N.lib.mifft_has_feature(N.FEATURE_AB_FORMS) == 1:        # (the 16-column persistent form of these lengths: `make DEV=1` builds)
-        N.check(N.lib.mifft_debug_set(N.DEBUG_NARROW_TILES, 1), "debug_set")
-        try:
-            monkeypatch.setenv("PYFFT_AMD_STRATEGY", "fused")
-            narrow = _execute(ctx, (n,), numpy.complex64, batch, data, expect="fused2")
-        finally:
-            N.check(N.lib.mifft_debug_set(N.DEBUG_NARROW_TILES, 0), "debug_set")
-        assert numpy.array_equal(narrow, got)
     monkeypatch.setenv("PYFFT_AMD_STRATEGY", "auto")
     for item in (0, batch // 2, batch - 1):
         ref = numpy.fft.fft(data[item * n:(item + 1) * n].astype(numpy.complex128))
@@ -464,12 +350,10 @@ SPLIT_1D_CASES = [(1 << 16, 1100, "fused2"), (1 << 17, 515, "fused2"), (1 << 18,
 
 
 @pytest.mark.parametrize("n,batch,expect", SPLIT_1D_CASES, ids=str)
-def test_split_planes_on_per_xcd_lists(ctx, monkeypatch, n, batch, expect):
+def test_split_planes_on_sibling_tiles(ctx, monkeypatch, n, batch, expect):
     """float32 planes (the reference's split layout, pyfft/plan.py:10-63 dtype rule) on the persistent 1-D kernels by the plan's own
     choice: the two 16-column tiles that share every 128-byte line of a plane run in one 512-thread work-group, interleaved at lane
-    level (fft_fused2s_kernel on the global list); with PYFFT_AMD_SPLIT_FUSEDX the per-XCD lists, where siblings share an L2 (2^16
-    ... 2^18).  The bits of the chain (same
-    tiles, same order of operations), in place == out of place, numpy with the reference's thresholds on sampled transforms, the
+    level (fft_fused2s_kernel).  The bits of the chain (same tiles, same order of operations), in place == out of place, numpy with the reference's thresholds on sampled transforms, the
     inverse round trip, batches that are no multiple of 8 (lists of unequal length)."""
     rng = numpy.random.default_rng(1400 + n % 97)
     re = _noise(rng, n * batch, numpy.float32)
@@ -490,11 +374,6 @@ def test_split_planes_on_per_xcd_lists(ctx, monkeypatch, n, batch, expect):
     back = _execute_split(ctx, (n,), numpy.float32, batch, got[0], got[1], inverse=True, expect=expect)
     x = re + 1j * im
     assert numpy.abs((back[0] + 1j * back[1]) - x).sum() / numpy.abs(x).sum() < 1.1e-6
-    from pyfft_amd import _native as N
-    if n <= (1 << 18) and N.lib.mifft_has_feature(N.FEATURE_FUSED2X) == 1:      # (`make DEV=1` builds)
-        monkeypatch.setenv("PYFFT_AMD_SPLIT_FUSEDX", "1")
-        lists = _execute_split(ctx, (n,), numpy.float32, batch, re, im, expect="fused2x")
-        assert numpy.array_equal(lists[0], got[0]) and numpy.array_equal(lists[1], got[1])
 
 
 # ---- persistent two-pair kernel for 3-D shapes with 64- and 128-point axes (csrc/fft_fusedp2.hip) --------------------------------

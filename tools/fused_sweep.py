@@ -2,8 +2,8 @@
 profiles/r04_fused_sweep.log): every variant builds a fresh plan in this process with the development switches of
 pyfft_amd/_debug.py set, checks sampled transforms against numpy and times back-to-back executes between two HIP events.
 
-    python3 tools/fused_sweep.py [SHAPE DTYPE GIB VARIANTS]...      e.g.  524288 complex64 1 auto,f:14:28,x:4:8:0
-    variants: auto | chain | pipelined | fused | f:LAG:RING (fused2 / fusedp) | x:LAG:RING:WT (fusedx, per XCD) | seq | any of them + @ENV=VALUE
+    python3 tools/fused_sweep.py [SHAPE DTYPE GIB VARIANTS]...      e.g.  524288 complex64 1 auto,f:14:28
+    variants: auto | chain | pipelined | fused | f:LAG:RING (fused2 / fusedp) | any of them + @ENV=VALUE
     GIB may be a fraction (0.03125 = the reference's 32 MiB protocol)
 
     python3 tools/fused_sweep.py --emit OUT.json [--gib 2]
@@ -19,8 +19,8 @@ import numpy
 from pyfft_amd.hip import Plan, DeviceArray, Event
 from pyfft_amd import _native as N
 
-KEYS = ("PYFFT_AMD_STRATEGY", "PYFFT_AMD_FUSED_RING", "PYFFT_AMD_FUSEDX", "PYFFT_AMD_FUSED3", "PYFFT_AMD_FUSED_WGS", "PYFFT_AMD_PIPE_MB", "PYFFT_AMD_PIPE_STREAMS",
-        "PYFFT_AMD_FUSED_MEMSET", "PYFFT_AMD_NO_FUSEDX", "PYFFT_AMD_SMALL_FUSED", "MIFFT_PAIR", "MIFFT_NARROW_TILES", "PYFFT_AMD_SPLIT_FUSEDX", "PYFFT_AMD_NO_SPLIT_ROWFIRST", "MIFFT_STORE", "PYFFT_AMD_NO_OOP_ND", "MIFFT_NO_ND2", "PYFFT_AMD_NO_ND_GENERIC", "MIFFT_NO_WAVE", "MIFFT_FORCE_WAVE", "MIFFT_ALT_ROWS")
+KEYS = ("PYFFT_AMD_STRATEGY", "PYFFT_AMD_FUSED_RING", "PYFFT_AMD_FUSED3", "PYFFT_AMD_FUSED_WGS", "PYFFT_AMD_PIPE_MB", "PYFFT_AMD_PIPE_STREAMS",
+        "PYFFT_AMD_FUSED_MEMSET", "MIFFT_PAIR", "MIFFT_NARROW_TILES", "PYFFT_AMD_NO_SPLIT_ROWFIRST", "MIFFT_STORE", "PYFFT_AMD_NO_OOP_ND", "MIFFT_NO_ND2", "PYFFT_AMD_NO_ND_GENERIC", "MIFFT_NO_WAVE", "MIFFT_FORCE_WAVE", "MIFFT_ALT_ROWS")
 
 
 def variant_env(v):
@@ -39,11 +39,6 @@ def variant_env(v):
         env["PYFFT_AMD_STRATEGY"] = "fused"
         env["PYFFT_AMD_FUSED_RING"] = "%s,%s" % (t[1], t[2])
         env["PYFFT_AMD_FUSED3"] = "%s,%s" % (t[1], t[2])
-    elif t[0] == "seq":          # tiny batches: the sequential single-launch work list
-        env["PYFFT_AMD_SMALL_FUSED"] = "1"
-    elif t[0] == "x":
-        env["PYFFT_AMD_STRATEGY"] = "fusedx"
-        env["PYFFT_AMD_FUSEDX"] = "%s,%s" % (t[1], t[2])
     else:
         raise ValueError(v)
     return env

@@ -1,4 +1,4 @@
-"""Soak of the persistent strategies (fused2 / fused2x / fusedp): every shape class that has such a kernel, both layouts, batches
+"""Soak of the persistent strategies (fused2 / fusedp): every shape class that has such a kernel, both layouts, batches
 just beyond the chain threshold, odd batches, batches that fill the ring exactly twice -- each executed three times back to back
 (alternating counter sets), out of place and in place, forward and inverse, and compared WHOLE-ARRAY with the chain strategy
 (one launch per pass over the whole batch) on the same numbers.  Development tool behind profiles/r04_persistent_soak.log.
@@ -57,7 +57,7 @@ def one(shape, dtype, batch, rng):
     os.environ["PYFFT_AMD_STRATEGY"] = "auto"
     plan = Plan(shape if len(shape) > 1 else shape[0], dtype=dt, wait_for_finish=True)
     strat = plan.strategy(batch)
-    if strat[0] not in ("fused2", "fused2x", "fusedp"):
+    if strat[0] not in ("fused2", "fusedp"):
         return strat, None
     os.environ["PYFFT_AMD_STRATEGY"] = "chain"
     cplan = Plan(shape if len(shape) > 1 else shape[0], dtype=dt, wait_for_finish=True)

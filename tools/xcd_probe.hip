@@ -1,5 +1,5 @@
 // XCD-level feasibility probe for a single-crossing N = 2^20 transform (development tool; results are kept under
-// profiles/r02_xcd_probe*.log).  Three questions, each one number the design of fft_xcd2.hpp depends on:
+// profiles/r02_xcd_probe*.log).  Three questions, each one number the design of the XCD-resident kernel (fft_xcd2.hpp, since retired) depended on:
 //   T1  census: how many of the 512 persistent work-groups land on each XCD (HW_REG_XCC_ID)
 //   T2  B1: the streaming bandwidth ONE XCD can pull when only k of the 8 XCDs stream (column-tile access
 //       pattern of the COL kernels: 256 threads x 64 eight-byte accesses in flight, non-temporal)
