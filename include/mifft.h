@@ -466,6 +466,42 @@ int mifft_mixed_nd_supported(int32_t precision, int32_t x, int32_t y, int32_t z)
 int mifft_launch_mixed_nd(int32_t precision, int32_t x, int32_t y, int32_t z, int64_t transforms, const void *in, void *out,
                           const void *tw_x, const void *tw_y, const void *tw_z, int32_t inverse, double scale, mifft_stream_t stream);
 
+/* Real-input transforms (docs/extensions.md "Real-input transforms").  A real array of shape (nz, ny, nx) read as interleaved complex
+ * numbers is the packed array z of shape (nz, ny, nx / 2); a complex transform of z plus one separation step gives the half spectrum
+ * X of shape (nz, ny, nx / 2 + 1) (numpy's rfftn layout), and one packing step plus an inverse complex transform undoes it.
+ * mifft_launch_real_post enqueues that step, one streaming launch over `outer` items:
+ *   inverse 0 (separation)  in = Z = FFT(z), nx / 2 complex numbers per row -> out = scale * X, nx / 2 + 1 per row
+ *   inverse 1 (packing)     in = X -> out = scale * Z' with IFFT(Z') (unnormalised) = the unnormalised inverse real transform of X,
+ *                           packed; the edge planes kx = 0 and kx = nx / 2 are read through their Hermitian parts
+ * Rows are dense within an item; stride_in / stride_out are the item pitches in complex numbers (at least the item's size on that
+ * side).  tw = device table w(nx)^k, k = 0 .. nx / 2 (nx / 2 + 1 entries, the precision's complex type).  Out of place only: in and out
+ * must not overlap.  nx >= 2, ny, nz >= 1, all powers of two; buffers aligned to one complex number. */
+typedef struct mifft_real_post {
+    int32_t precision;   /* MIFFT_F32 / MIFFT_F64 */
+    int32_t inverse;     /* 0 separation, 1 packing */
+    int32_t nx, ny, nz;  /* REAL shape of one item: x contiguous */
+    int32_t reserved;    /* 0 */
+    int64_t outer;       /* items */
+    int64_t stride_in;   /* item pitch of `in`, complex numbers */
+    int64_t stride_out;  /* item pitch of `out`, complex numbers */
+    const void *in;
+    void *out;
+    const void *tw;
+    double scale;
+} mifft_real_post;
+int mifft_launch_real_post(const mifft_real_post *desc, mifft_stream_t stream);
+
+/* One-launch real-input rows: forward, `rows` real rows of n points (dense, n reals each) -> their half spectra (dense, n / 2 + 1
+ * complex numbers each), = scale * numpy.fft.rfft per row; inverse, half spectra -> real rows, = scale * the unnormalised inverse real
+ * transform (X[0] and X[n / 2] through their real parts).  The row transform of the n / 2 packed points and the separation / packing
+ * run in one work-group, so a row crosses HBM once.  tw_half = device table w(n / 2)^k (n / 2 entries), tw_sep = w(n)^k (n / 2 + 1
+ * entries), the precision's complex type.  Out of place only.
+ *   mifft_real_row_supported   0 if a kernel exists for the real length n (every n / 2 with a ROW kernel, n >= 4: up to 65536 fp32,
+ *                              32768 fp64), else MIFFT_E_UNSUPPORTED */
+int mifft_real_row_supported(int32_t precision, int32_t n);
+int mifft_launch_real_row(int32_t precision, int32_t n, int32_t inverse, int64_t rows, const void *in, void *out, const void *tw_half,
+                          const void *tw_sep, double scale, mifft_stream_t stream);
+
 /* Same as mifft_launch_chain but brackets the chain with two events on `stream` and, after
  * synchronising, reports the elapsed device time of `repeats` back-to-back chains. (bench/test helper) */
 int mifft_time_chain(const mifft_pass *passes, int32_t npasses, void *const bufs0[3], void *const bufs1[3],

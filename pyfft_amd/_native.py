@@ -129,6 +129,25 @@ class MifftFusedSync(ctypes.Structure):
     ]
 
 
+class MifftRealPost(ctypes.Structure):
+    """struct mifft_real_post (include/mifft.h): the separation / packing step of a real-input transform."""
+    _fields_ = [
+        ("precision", ctypes.c_int32),
+        ("inverse", ctypes.c_int32),
+        ("nx", ctypes.c_int32),
+        ("ny", ctypes.c_int32),
+        ("nz", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("outer", ctypes.c_int64),
+        ("stride_in", ctypes.c_int64),
+        ("stride_out", ctypes.c_int64),
+        ("in_", ctypes.c_void_p),
+        ("out", ctypes.c_void_p),
+        ("tw", ctypes.c_void_p),
+        ("scale", ctypes.c_double),
+    ]
+
+
 _vp = ctypes.c_void_p
 _vpp = ctypes.POINTER(ctypes.c_void_p)
 _i32 = ctypes.c_int32
@@ -205,6 +224,9 @@ PROTOTYPES = {
                                                    _i32, ctypes.c_double, _vp]),
     "mifft_mixed_nd_supported": (ctypes.c_int, [_i32, _i32, _i32, _i32]),
     "mifft_launch_mixed_nd": (ctypes.c_int, [_i32, _i32, _i32, _i32, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _i32, ctypes.c_double, _vp]),
+    "mifft_launch_real_post": (ctypes.c_int, [ctypes.POINTER(MifftRealPost), _vp]),
+    "mifft_real_row_supported": (ctypes.c_int, [_i32, _i32]),
+    "mifft_launch_real_row": (ctypes.c_int, [_i32, _i32, _i32, ctypes.c_int64, _vp, _vp, _vp, _vp, ctypes.c_double, _vp]),
     "mifft_time_chain": (ctypes.c_int, [_pass_p, _i32, _vpp, _vpp, _vp, _i32, ctypes.POINTER(ctypes.c_float)]),
 }
 

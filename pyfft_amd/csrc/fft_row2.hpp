@@ -50,10 +50,13 @@ __device__ __forceinline__ int row2_pad(int i) { return i + (i >> 4); }
 // instead of L complex numbers: twice the barriers, half the LDS, so twice the work-groups per CU for the longest rows.
 // LAY (second batch of round 4): bit 0 = the input is two scalar planes (inb / inb1 = the row's first real / imaginary scalar), bit 1 =
 // the output likewise (outb / outb1); 0 = interleaved complex numbers on both sides.
-template <typename T, int L, int TPR, int Ns, bool FIRST, bool HALF, typename RL, int LAY = 0> struct Row2Stages;
+// EPI (real-input rows, fft_real_row.hpp): a type whose EPI::run<NB, R, TPR, LR>(lds, v, a, tid, outb, valid) replaces the last stage's
+// stores -- it receives the transform in registers (v[b*R + k] = point b*TPR + k*LR + tid) and writes what it derives from it.  void:
+// the plain stores below, unchanged.
+template <typename T, int L, int TPR, int Ns, bool FIRST, bool HALF, typename RL, int LAY = 0, typename EPI = void> struct Row2Stages;
 
-template <typename T, int L, int TPR, int Ns, bool FIRST, bool HALF, int R, int... Rest, int LAY>
-struct Row2Stages<T, L, TPR, Ns, FIRST, HALF, RadixList<R, Rest...>, LAY> {
+template <typename T, int L, int TPR, int Ns, bool FIRST, bool HALF, int R, int... Rest, int LAY, typename EPI>
+struct Row2Stages<T, L, TPR, Ns, FIRST, HALF, RadixList<R, Rest...>, LAY, EPI> {
     static constexpr int NT = TPR;
     static constexpr int PPT = L / NT;
     static constexpr int NB = PPT / R;
@@ -189,7 +192,9 @@ struct Row2Stages<T, L, TPR, Ns, FIRST, HALF, RadixList<R, Rest...>, LAY> {
             }
             Dft<R, T>::run(v + b * R);
         });
-        if constexpr (LAST) {
+        if constexpr (LAST && !std::is_void<EPI>::value) {
+            EPI::template run<NB, R, NT, LR>(lds, v, a, tid, outb, valid);
+        } else if constexpr (LAST) {
             const T sx = (T)a.scale;
             const T sy = a.inverse ? -sx : sx;
             if (valid) {
@@ -228,7 +233,7 @@ struct Row2Stages<T, L, TPR, Ns, FIRST, HALF, RadixList<R, Rest...>, LAY> {
                 if (a.nt & 4) stores(IC<2>{}); else if (a.nt & 2) stores(IC<1>{}); else stores(IC<0>{});
             }
         } else {
-            using Next = Row2Stages<T, L, TPR, Ns * R, false, HALF, RadixList<Rest...>, LAY>;
+            using Next = Row2Stages<T, L, TPR, Ns * R, false, HALF, RadixList<Rest...>, LAY, EPI>;
             if constexpr (!FIRST) __syncthreads();  // everybody has fetched its operands of this stage
             if constexpr (!HALF) {
                 spill<0>(lds, v, tid);

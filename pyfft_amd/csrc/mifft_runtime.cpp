@@ -1323,6 +1323,71 @@ int mifft_launch_mixed_nd(int32_t precision, int32_t x, int32_t y, int32_t z, in
     return 0;
 }
 
+int mifft_launch_real_post(const mifft_real_post* d, mifft_stream_t stream) {
+    if (!d) return set_err(MIFFT_E_INVALID, "real post: null descriptor");
+    if (d->precision != MIFFT_F32 && d->precision != MIFFT_F64) return set_err(MIFFT_E_INVALID, "real post: bad precision %d", d->precision);
+    if (d->inverse != 0 && d->inverse != 1) return set_err(MIFFT_E_INVALID, "real post: inverse must be 0 or 1");
+    if (d->nx < 2 || !is_pow2(d->nx) || !is_pow2(d->ny) || !is_pow2(d->nz))
+        return set_err(MIFFT_E_INVALID, "real post: shape %d x %d x %d is not powers of two with nx >= 2", d->nz, d->ny, d->nx);
+    if (d->outer < 0) return set_err(MIFFT_E_INVALID, "real post: negative item count");
+    if (!d->in || !d->out || !d->tw) return set_err(MIFFT_E_INVALID, "real post: null buffer");
+    if (d->reserved != 0) return set_err(MIFFT_E_INVALID, "real post: reserved field must be 0");
+    const long long L = d->nx / 2, rows = (long long)d->ny * d->nz;
+    const long long n_in = rows * (d->inverse ? L + 1 : L), n_out = rows * (d->inverse ? L : L + 1);
+    if (d->stride_in < n_in || d->stride_out < n_out) return set_err(MIFFT_E_INVALID, "real post: item pitch below the item's size");
+    const long long esz = d->precision == MIFFT_F64 ? 16 : 8;
+    if (((uintptr_t)d->in | (uintptr_t)d->out | (uintptr_t)d->tw) & (uintptr_t)(esz - 1))
+        return set_err(MIFFT_E_INVALID, "real post: buffers must be aligned to one complex number");
+    if (mul3_checked(d->outer, d->stride_in, esz) < 0 || mul3_checked(d->outer, d->stride_out, esz) < 0)
+        return set_err(MIFFT_E_INVALID, "real post: items * pitch overflows");
+    if (d->outer == 0) return 0;
+    const uintptr_t i0 = (uintptr_t)d->in, i1 = i0 + (uintptr_t)(((d->outer - 1) * d->stride_in + n_in) * esz);
+    const uintptr_t o0 = (uintptr_t)d->out, o1 = o0 + (uintptr_t)(((d->outer - 1) * d->stride_out + n_out) * esz);
+    if (i0 < o1 && o0 < i1) return set_err(MIFFT_E_INVALID, "real post: input and output overlap (out of place only)");
+    const int rc = mifft_real_post_launch(d->precision == MIFFT_F64, d->inverse, d->nx, d->ny, d->nz, d->outer, d->stride_in, d->stride_out,
+                                          d->in, d->out, d->tw, d->scale, (hipStream_t)stream);
+    if (rc == -1) return set_err(MIFFT_E_INVALID, "grid too large");
+    if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
+    return 0;
+}
+int mifft_real_row_supported(int32_t precision, int32_t n) {
+    if ((precision != MIFFT_F32 && precision != MIFFT_F64) || n < 4 || !is_pow2(n)) return MIFFT_E_UNSUPPORTED;
+    const int rc = precision == MIFFT_F64 ? mifft_real_row_dispatch_f64(n / 2, 0, nullptr, nullptr, 1)
+                                          : mifft_real_row_dispatch_f32(n / 2, 0, nullptr, nullptr, 1);
+    return rc == 0 ? 0 : MIFFT_E_UNSUPPORTED;
+}
+int mifft_launch_real_row(int32_t precision, int32_t n, int32_t inverse, int64_t rows, const void* in, void* out, const void* tw_half,
+                          const void* tw_sep, double scale, mifft_stream_t stream) {
+    if (precision != MIFFT_F32 && precision != MIFFT_F64) return set_err(MIFFT_E_INVALID, "real row: bad precision %d", precision);
+    if (n < 2 || !is_pow2(n)) return set_err(MIFFT_E_INVALID, "real row: n = %d is not a power of two >= 2", n);
+    if (mifft_real_row_supported(precision, n) != 0) return set_err(MIFFT_E_UNSUPPORTED, "real row: no kernel for n = %d", n);
+    if (inverse != 0 && inverse != 1) return set_err(MIFFT_E_INVALID, "real row: inverse must be 0 or 1");
+    if (rows < 0) return set_err(MIFFT_E_INVALID, "real row: negative row count");
+    if (!in || !out || !tw_half || !tw_sep) return set_err(MIFFT_E_INVALID, "real row: null buffer");
+    const long long esz = precision == MIFFT_F64 ? 16 : 8;
+    if (((uintptr_t)in | (uintptr_t)out | (uintptr_t)tw_half | (uintptr_t)tw_sep) & (uintptr_t)(esz - 1))
+        return set_err(MIFFT_E_INVALID, "real row: buffers must be aligned to one complex number");
+    const long long L = n / 2, n_in = inverse ? L + 1 : L, n_out = inverse ? L : L + 1;
+    if (mul3_checked(rows, n_in + n_out, esz) < 0) return set_err(MIFFT_E_INVALID, "real row: rows * n overflows");
+    if (rows == 0) return 0;
+    const uintptr_t i0 = (uintptr_t)in, i1 = i0 + (uintptr_t)(rows * n_in * esz);
+    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (uintptr_t)(rows * n_out * esz);
+    if (i0 < o1 && o0 < i1) return set_err(MIFFT_E_INVALID, "real row: input and output overlap (out of place only)");
+    mifft::TileArgs a = {};
+    a.in0 = in;
+    a.out0 = out;
+    a.tw_L = tw_half;
+    a.tw_lo = tw_sep;
+    a.total = rows;
+    a.inverse = inverse;
+    a.scale = scale;
+    const int rc = precision == MIFFT_F64 ? mifft_real_row_dispatch_f64((int)L, inverse, &a, (hipStream_t)stream, 0)
+                                          : mifft_real_row_dispatch_f32((int)L, inverse, &a, (hipStream_t)stream, 0);
+    if (rc == -2) return set_err(MIFFT_E_UNSUPPORTED, "real row: no kernel for n = %d", n);
+    if (rc == -1) return set_err(MIFFT_E_INVALID, "grid too large");
+    if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
+    return 0;
+}
 int mifft_time_chain(const mifft_pass* passes, int32_t npasses, void* const bufs0[3], void* const bufs1[3], mifft_stream_t stream,
                      int32_t repeats, float* ms_total) {
     if (!ms_total || repeats < 1) return set_err(MIFFT_E_INVALID, "bad timing arguments");

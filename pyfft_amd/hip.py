@@ -587,6 +587,8 @@ def Plan(*args, **kwds):
     built for a device that is not the caller's current one makes it current around its own calls and restores the
     caller's afterwards, so one process can hold a plan per GPU (buffers must live on the plan's device).
     `mempool`: any object with an allocate(nbytes) method returning a buffer-like object.
+    `real=True`: real-input transforms (pyfft_amd/real.py): `dtype` float32 / float64 (or complex64 / complex128) names the precision,
+    execute(real_in, spectrum_out) / execute(spectrum_in, real_out, inverse=True), out of place, numpy's rfftn / irfftn layout.
     `parent_shape=`, `any_size=True`: opt-in extensions (tiles of a bigger array; sizes that are not powers of two), see
     pyfft_amd/generic.py.  Without them a size that is not a power of two is a ValueError, as in the reference.
     `fast_math`: accepted for signature parity and ignored -- the reference passes -use_fast_math to nvcc for its on-device
@@ -599,7 +601,11 @@ def Plan(*args, **kwds):
     # opt-in extensions the reference lists as TODO (TODO.txt:6-8; pyfft_amd/generic.py): tiles of a parent array, any size
     parent_shape = kwds.pop('parent_shape', None)
     any_size = bool(kwds.pop('any_size', False))
-    generic = parent_shape is not None or any_size
+    # opt-in real-input transforms (pyfft_amd/real.py): dtype names the real precision, the spectrum is numpy's rfftn half spectrum
+    real = bool(kwds.pop('real', False))
+    if real and (parent_shape is not None or any_size):
+        raise ValueError("pyfft_amd: real=True cannot be combined with any_size= or parent_shape=")
+    generic = (parent_shape is not None or any_size) and not real
     if generic and parent_shape is None:
         # any_size=True on a power-of-two shape: the dense plan itself (no work array, no gather / scatter)
         shape = args[0] if args else kwds.get('shape')
@@ -610,7 +616,10 @@ def Plan(*args, **kwds):
             pass
 
     # argument errors first (ValueError, as in the reference), then the device
-    if not generic:
+    if real:
+        from .real import RealFFTPlan
+        RealFFTPlan.validate(*args, **kwds)
+    elif not generic:
         FFTPlan.validate(*args, **kwds)
     if device_count() < 1:
         raise RuntimeError("pyfft_amd: no HIP device visible (there is no CPU fallback)")
@@ -637,6 +646,8 @@ def Plan(*args, **kwds):
     context = Context(device, stream_obj, mempool)
     prev = context.activate()       # context=i: tables and scratch are allocated on device i
     try:
+        if real:
+            return RealFFTPlan(context, *args, **kwds)
         if generic:
             from .generic import GenericFFTPlan
             return GenericFFTPlan(context, *args, parent_shape=parent_shape, any_size=any_size, **kwds)
