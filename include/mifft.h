@@ -502,6 +502,29 @@ int mifft_real_row_supported(int32_t precision, int32_t n);
 int mifft_launch_real_row(int32_t precision, int32_t n, int32_t inverse, int64_t rows, const void *in, void *out, const void *tw_half,
                           const void *tw_sep, double scale, mifft_stream_t stream);
 
+/* Half-precision (complex32) transforms (docs/extensions.md "Half-precision transforms"): interleaved fp16 data, one fp16 real and one
+ * fp16 imaginary part per point (4 bytes).  Loads widen to fp32 exactly, every stage runs in fp32 on the fp32 twiddle tables, and the
+ * result (times scale, in fp32) is rounded to fp16 once, to nearest even, at the store: beyond +-65504 it is +-inf, NaN stays NaN.
+ * One launch over `transforms` dense transforms of the (z, y, x) shape, x contiguous; in place (in == out) or out of place.
+ *   mifft_half_supported   0 for the one-launch shapes of interleaved fp32 data -- 1-D rows (y = z = 1) of 2 ... 32768 points, and
+ *                          every shape with y or z > 1 for which mifft_nd_shape_supported(MIFFT_F32, x, y, z,
+ *                          MIFFT_VARIANT_INTERLEAVED_ONLY) is 0 -- else MIFFT_E_UNSUPPORTED
+ *   mifft_half_kernel      the kernel family such a shape runs after its unit axes are dropped (MIFFT_HALF_KERNEL_*), else
+ *                          MIFFT_E_UNSUPPORTED.  variant 0: the fixed-shape N-D kernel where one exists; variant 1: the run-time-
+ *                          shaped one wherever it takes the shape (up to mifft_nd_max_points_for(MIFFT_F32) points), as variant 1
+ *                          of an fp32 MIFFT_PASS_ND pass does; 1-D rows ignore it
+ *   mifft_launch_half      tw_x / tw_y / tw_z = device tables w(len)^k, k < len, of complex64 numbers (8-byte aligned; null for an axis
+ *                          of one point); in / out 16-byte aligned, equal or not overlapping; inverse 0 forward, 1 unnormalised
+ *                          inverse (conjugate exponent), both times `scale`; variant as for mifft_half_kernel. */
+#define MIFFT_HALF_KERNEL_TILE 1  /* LDS-staged ROW tile (fft_tile.hpp), rows of 2 ... 128 points */
+#define MIFFT_HALF_KERNEL_ROW  2  /* register-edged row (fft_row2.hpp), 256 ... 32768 points */
+#define MIFFT_HALF_KERNEL_ND2  3  /* fixed-shape N-D kernel (fft_nd2.hpp) */
+#define MIFFT_HALF_KERNEL_ND   4  /* run-time-shaped N-D kernel (fft_nd.hpp), up to 16384 points */
+int mifft_half_supported(int32_t x, int32_t y, int32_t z);
+int mifft_half_kernel(int32_t x, int32_t y, int32_t z, int32_t variant);
+int mifft_launch_half(int32_t x, int32_t y, int32_t z, int32_t variant, int32_t inverse, int64_t transforms, const void *in, void *out, const void *tw_x,
+                      const void *tw_y, const void *tw_z, double scale, mifft_stream_t stream);
+
 /* Same as mifft_launch_chain but brackets the chain with two events on `stream` and, after
  * synchronising, reports the elapsed device time of `repeats` back-to-back chains. (bench/test helper) */
 int mifft_time_chain(const mifft_pass *passes, int32_t npasses, void *const bufs0[3], void *const bufs1[3],

@@ -31,6 +31,7 @@ FLAG_SRC_INTERLEAVED, FLAG_DST_INTERLEAVED = 1, 2
 FLAG_STREAM_SRC, FLAG_STREAM_DST = 4, 8
 FLAG_WRITE_THROUGH = 32
 FLAG_PAIR_WITH_NEXT = 16
+HALF_KERNEL_TILE, HALF_KERNEL_ROW, HALF_KERNEL_ND2, HALF_KERNEL_ND = 1, 2, 3, 4    # mifft_half_kernel
 FUSED2_COUNTER_STRIDE = 64          # MIFFT_FUSED2_COUNTER_STRIDE (uint32 words between two counters)
 
 
@@ -227,6 +228,9 @@ PROTOTYPES = {
     "mifft_launch_real_post": (ctypes.c_int, [ctypes.POINTER(MifftRealPost), _vp]),
     "mifft_real_row_supported": (ctypes.c_int, [_i32, _i32]),
     "mifft_launch_real_row": (ctypes.c_int, [_i32, _i32, _i32, ctypes.c_int64, _vp, _vp, _vp, _vp, ctypes.c_double, _vp]),
+    "mifft_half_supported": (ctypes.c_int, [_i32, _i32, _i32]),
+    "mifft_half_kernel": (ctypes.c_int, [_i32, _i32, _i32, _i32]),
+    "mifft_launch_half": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _vp]),
     "mifft_time_chain": (ctypes.c_int, [_pass_p, _i32, _vpp, _vpp, _vp, _i32, ctypes.POINTER(ctypes.c_float)]),
 }
 

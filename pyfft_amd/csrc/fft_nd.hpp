@@ -44,7 +44,8 @@ __device__ __forceinline__ int nd_pad(int i) { return i + (i >> 4); }
 
 // EDGE (last stage of all): results scaled (and conjugated back for the inverse) straight to HBM; `gout` = first byte of
 // the tile, `left` = points from the start of the tile to the end of the data (whole transforms are in or out).
-template <typename T, int P, int NT, int R, bool EDGE>
+// ST: storage type of those stores (fft_tile.hpp: narrow)
+template <typename T, int P, int NT, int R, bool EDGE, typename ST = T>
 __device__ __forceinline__ void nd_stage(cplx<T>* lds, cplx<T>* v, const cplx<T>* tw, int logL, int logS, int logNs, int tid,
                                          char* gout, long long left, T sx, T sy) {
     constexpr int PPT = P / NT;
@@ -104,7 +105,7 @@ __device__ __forceinline__ void nd_stage(cplx<T>* lds, cplx<T>* v, const cplx<T>
                     p.x *= sx;
                     p.y *= sy;
                     const unsigned idx = (unsigned)(base[b] + ((idxD + (k << logNs)) << logS));
-                    *reinterpret_cast<cplx<T>*>(gout + idx * (unsigned)sizeof(cplx<T>)) = p;
+                    *reinterpret_cast<cplx<ST>*>(gout + idx * (unsigned)sizeof(cplx<ST>)) = narrow<T, ST>(p);
                 });
             }
         } else {
@@ -117,8 +118,12 @@ __device__ __forceinline__ void nd_stage(cplx<T>* lds, cplx<T>* v, const cplx<T>
     if constexpr (!EDGE) __syncthreads();
 }
 
-template <typename T, int P, int NT>
+// TS = Complex32<T> (fft_tile.hpp): complex32 storage, interleaved data, plain stores (wt is ignored)
+template <typename TS, int P, int NT>
 __global__ void __launch_bounds__(NT) fft_nd_kernel(const NdArgs a) {
+    using T = typename StorageOf<TS>::work;
+    using ST = typename StorageOf<TS>::store;
+    constexpr bool kST = !std::is_same<T, ST>::value;
     constexpr int PPT = P / NT;
     static_assert(PPT * NT == P && PPT % 4 == 0, "bad tile");
     __shared__ __attribute__((aligned(16))) cplx<T> lds[P + P / 16];
@@ -138,7 +143,11 @@ __global__ void __launch_bounds__(NT) fft_nd_kernel(const NdArgs a) {
             const int e = (it * NT + tid) * V;
             cplx<T> p[V];
             static_for<V>([&](auto k) { p[k].x = 0; p[k].y = 0; });
-            if (g0 + e < a.total) load_vec<T, V>(io, g0 + e, p);
+            if constexpr (kST) {
+                if (g0 + e < a.total) load_pair_st<T, ST>(a.in0, g0 + e, p);
+            } else {
+                if (g0 + e < a.total) load_vec<T, V>(io, g0 + e, p);
+            }
             static_for<V>([&](auto k) { v[V * it + k] = p[k]; });
         });
         static_for<PPT / V>([&](auto ii) {
@@ -152,20 +161,21 @@ __global__ void __launch_bounds__(NT) fft_nd_kernel(const NdArgs a) {
             });
         });
     };
-    if (a.split) load_phase(IC<4>{}); else load_phase(IC<2>{});
+    if constexpr (kST) load_phase(IC<2>{});
+    else if (a.split) load_phase(IC<4>{}); else load_phase(IC<2>{});
     __syncthreads();
 
     const T sx = (T)a.scale;
     const T sy = a.inverse ? -sx : sx;
     const long long left = a.total - g0;
-    char* gout = reinterpret_cast<char*>(reinterpret_cast<cplx<T>*>(a.out0) + g0);
+    char* gout = reinterpret_cast<char*>(reinterpret_cast<cplx<ST>*>(a.out0) + g0);
     for (int s = 0; s < a.nstages; ++s) {
         const int ax = a.st_axis[s];
         const cplx<T>* tw = reinterpret_cast<const cplx<T>*>(a.tw[ax]);
         const int logL = a.logL[ax], logS = a.logS[ax], logNs = a.st_logNs[s];
         const bool edge = s + 1 == a.nstages && a.edge_out;
 #define MIFFT_ND_STAGE(R)                                                                          \
-    if (edge) nd_stage<T, P, NT, R, true>(lds, v, tw, logL, logS, logNs, tid, gout, left, sx, sy); \
+    if (edge) nd_stage<T, P, NT, R, true, ST>(lds, v, tw, logL, logS, logNs, tid, gout, left, sx, sy); \
     else nd_stage<T, P, NT, R, false>(lds, v, tw, logL, logS, logNs, tid, gout, left, sx, sy);
         switch (a.st_radix[s]) {
             case 2: MIFFT_ND_STAGE(2) break;
@@ -191,10 +201,16 @@ __global__ void __launch_bounds__(NT) fft_nd_kernel(const NdArgs a) {
                 p[k].x *= sx;
                 p[k].y *= sy;
             });
-            if (g0 + e < a.total) store_vec<T, V, NTS>(io, g0 + e, p);
+            if constexpr (kST) {
+                if (g0 + e < a.total) store_pair_st<T, ST>(a.out0, g0 + e, p);
+            } else {
+                if (g0 + e < a.total) store_vec<T, V, NTS>(io, g0 + e, p);
+            }
         });
     };
-    if (a.wt) {
+    if constexpr (kST) {
+        store_phase(IC<2>{}, IC<0>{});
+    } else if (a.wt) {
         if (a.split_out) store_phase(IC<4>{}, IC<2>{}); else store_phase(IC<2>{}, IC<2>{});
     } else {
         if (a.split_out) store_phase(IC<4>{}, IC<0>{}); else store_phase(IC<2>{}, IC<0>{});

@@ -83,41 +83,47 @@ template <typename T, int P, int NT, bool HALF, typename D> struct Nd2Stage {
     }
     // operands straight from HBM: `inb` = first byte of the transform (wave-uniform)
     // `left` = points from the start of the tile to the end of the data (whole transforms are in or out of range)
-    template <bool NTL = false>
+    // ST: storage type (fft_tile.hpp: widen / narrow), here and in store()
+    template <bool NTL = false, typename ST = T>
     static __device__ __forceinline__ void load(const char* inb, cplx<T>* v, int tid, long long left) {
         static_for<NB>([&](auto bb) {
             constexpr int b = bb;
             int base, jb;
             geom(b, tid, base, jb);
-            const unsigned voff = (unsigned)(base + jb * SA) * (unsigned)sizeof(cplx<T>);
+            const unsigned voff = (unsigned)(base + jb * SA) * (unsigned)sizeof(cplx<ST>);
             const bool ok = base < left;
             static_for<R>([&](auto kk) {
                 constexpr int k = kk;
                 cplx<T> p;
                 p.x = 0; p.y = 0;
                 if (ok) {
-                    const cplx<T>* q = reinterpret_cast<const cplx<T>*>(inb + (size_t)(k * LR * SA) * sizeof(cplx<T>) + voff);
-                    if constexpr (NTL) p = __builtin_nontemporal_load(q);
-                    else p = *q;
+                    const cplx<ST>* q = reinterpret_cast<const cplx<ST>*>(inb + (size_t)(k * LR * SA) * sizeof(cplx<ST>) + voff);
+                    if constexpr (NTL) p = widen<T, ST>(__builtin_nontemporal_load(q));
+                    else p = widen<T, ST>(*q);
                 }
                 v[b * R + k] = p;
             });
         });
     }
     // NTS: 0 plain, 1 non-temporal, 2 write-through (sc1) stores
-    template <int NTS = 0>
+    template <int NTS = 0, typename ST = T>
     static __device__ __forceinline__ void store(char* outb, const cplx<T>* v, int tid, T sx, T sy, long long left) {
         static_for<NB>([&](auto bb) {
             constexpr int b = bb;
             int base, jb;
             geom(b, tid, base, jb);
-            const unsigned voff = (unsigned)(base + idxd(jb) * SA) * (unsigned)sizeof(cplx<T>);
+            const unsigned voff = (unsigned)(base + idxd(jb) * SA) * (unsigned)sizeof(cplx<ST>);
             if (base < left) {
                 static_for<R>([&](auto kk) {
                     constexpr int k = kk;
                     cplx<T> p = v[b * R + k];
                     p.x *= sx;
                     p.y *= sy;
+                    if constexpr (!std::is_same<T, ST>::value) {
+                        static_assert(NTS == 0, "complex32: plain stores only");
+                        *reinterpret_cast<cplx<ST>*>(outb + (size_t)(k * Ns * SA) * sizeof(cplx<ST>) + voff) = narrow<T, ST>(p);
+                        return;
+                    }
                     char* kb = outb + (size_t)(k * Ns * SA) * sizeof(cplx<T>);
                     cplx<T>* q = reinterpret_cast<cplx<T>*>(kb + voff);
                     if constexpr (NTS == 2) store_wt<T>(kb, voff, p);
@@ -141,10 +147,11 @@ template <typename T, int P, int NT, bool HALF, typename D> struct Nd2Stage {
     }
 };
 
-template <typename T, int P, int NT, bool HALF, bool FIRST, typename SL> struct Nd2Chain;
+// ST: storage type of the last stage's stores
+template <typename T, int P, int NT, bool HALF, bool FIRST, typename SL, typename ST = T> struct Nd2Chain;
 
-template <typename T, int P, int NT, bool HALF, bool FIRST, typename D, typename... Rest>
-struct Nd2Chain<T, P, NT, HALF, FIRST, Nd2StageList<D, Rest...>> {
+template <typename T, int P, int NT, bool HALF, bool FIRST, typename D, typename... Rest, typename ST>
+struct Nd2Chain<T, P, NT, HALF, FIRST, Nd2StageList<D, Rest...>, ST> {
     using St = Nd2Stage<T, P, NT, HALF, D>;
     using LdsT = typename St::LdsT;
     static constexpr bool LAST = sizeof...(Rest) == 0;
@@ -153,12 +160,14 @@ struct Nd2Chain<T, P, NT, HALF, FIRST, Nd2StageList<D, Rest...>> {
     static __device__ __forceinline__ void run(LdsT* lds, cplx<T>* v, const cplx<T>* const* tw, int tid, char* outb, T sx,
                                                T sy, long long left, int nt_out) {
         St::compute(v, tw[D::AX], tid);
-        if constexpr (LAST) {
+        if constexpr (LAST && !std::is_same<T, ST>::value) {
+            St::template store<0, ST>(outb, v, tid, sx, sy, left);
+        } else if constexpr (LAST) {
             if (nt_out == 2) St::template store<2>(outb, v, tid, sx, sy, left);
             else if (nt_out == 1) St::template store<1>(outb, v, tid, sx, sy, left);  // MIFFT_FLAG_STREAM_DST
             else St::template store<0>(outb, v, tid, sx, sy, left);
         } else {
-            using NextChain = Nd2Chain<T, P, NT, HALF, false, Nd2StageList<Rest...>>;
+            using NextChain = Nd2Chain<T, P, NT, HALF, false, Nd2StageList<Rest...>, ST>;
             using Next = typename NextChain::St;
             if constexpr (!FIRST) __syncthreads();  // everybody has fetched its operands of this stage
             if constexpr (!HALF) {
@@ -231,9 +240,13 @@ template <typename D, typename... Rest> struct Nd2First<Nd2StageList<D, Rest...>
 
 // A tile of P points = P / (LX*LY*LZ) whole (LZ, LY, LX) transforms (x contiguous) per work-group.  TileArgs: in0 / out0
 // interleaved, total = number of POINTS, tw_L / tw_lo / tw_hi = w(LX) / w(LY) / w(LZ) tables, inverse, scale.
-template <typename T, int LX, int LY, int LZ, int P, int NT, bool HALF, int OCC, bool EDGE_IN, typename RLX, typename RLY,
+// TS = Complex32<T> (fft_tile.hpp): complex32 storage, plain accesses (the nt bits are ignored)
+template <typename TS, int LX, int LY, int LZ, int P, int NT, bool HALF, int OCC, bool EDGE_IN, typename RLX, typename RLY,
           typename RLZ>
 __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(OCC))) fft_nd2_kernel(const TileArgs a) {
+    using T = typename StorageOf<TS>::work;
+    using ST = typename StorageOf<TS>::store;
+    constexpr bool kST = !std::is_same<T, ST>::value;
     constexpr int PPT = P / NT;
     static_assert(PPT * NT == P && P % (LX * LY * LZ) == 0 && PPT % 2 == 0, "bad tile");
     static_assert(EDGE_IN || !HALF, "the linear-load form is built for full-complex exchanges only");
@@ -247,14 +260,16 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(OCC))) 
     const int tid = threadIdx.x;
     const long long g0 = (long long)blockIdx.x * P;
     const long long left = a.total - g0;
-    const char* inb = reinterpret_cast<const char*>(reinterpret_cast<const cplx<T>*>(a.in0) + g0);
-    char* outb = reinterpret_cast<char*>(reinterpret_cast<cplx<T>*>(a.out0) + g0);
+    const char* inb = reinterpret_cast<const char*>(reinterpret_cast<const cplx<ST>*>(a.in0) + g0);
+    char* outb = reinterpret_cast<char*>(reinterpret_cast<cplx<ST>*>(a.out0) + g0);
     const cplx<T>* tw[3] = {reinterpret_cast<const cplx<T>*>(a.tw_L), reinterpret_cast<const cplx<T>*>(a.tw_lo),
                             reinterpret_cast<const cplx<T>*>(a.tw_hi)};
     const T sx = (T)a.scale;
     const T sy = a.inverse ? -sx : sx;
     cplx<T> v[PPT];
-    if constexpr (EDGE_IN) {
+    if constexpr (EDGE_IN && kST) {
+        First::template load<false, ST>(inb, v, tid, left);
+    } else if constexpr (EDGE_IN) {
         if (a.nt & 1) First::template load<true>(inb, v, tid, left);  // MIFFT_FLAG_STREAM_SRC
         else First::template load<false>(inb, v, tid, left);
     } else {
@@ -263,9 +278,15 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(OCC))) 
         static_for<PPT / 2>([&](auto ii) {
             constexpr int it = ii;
             const unsigned e = (unsigned)(it * NT + tid) * 2u;
+            if constexpr (kST) {
+                v[2 * it] = cplx<T>{0, 0};
+                v[2 * it + 1] = cplx<T>{0, 0};
+                if ((long long)e < left) load_pair_st<T, ST>(inb, e, v + 2 * it);
+            } else {
             V4 q = {0, 0, 0, 0};
             if ((long long)e < left) q = *reinterpret_cast<const V4*>(inb + e * (unsigned)sizeof(cplx<T>));
             v[2 * it].x = q.x; v[2 * it].y = q.y; v[2 * it + 1].x = q.z; v[2 * it + 1].y = q.w;
+            }
         });
         static_for<PPT / 2>([&](auto ii) {
             constexpr int it = ii;
@@ -278,7 +299,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(OCC))) 
         __syncthreads();
     }
     if (a.inverse) static_for<PPT>([&](auto i) { v[i].y = -v[i].y; });
-    Nd2Chain<T, P, NT, HALF, true, SL>::run(lds, v, tw, tid, outb, sx, sy, left, (a.nt & 4) ? 2 : ((a.nt & 2) ? 1 : 0));
+    Nd2Chain<T, P, NT, HALF, true, SL, ST>::run(lds, v, tw, tid, outb, sx, sy, left, (a.nt & 4) ? 2 : ((a.nt & 2) ? 1 : 0));
 }
 
 template <typename T, int LX, int LY, int LZ, int P, int NT, bool HALF, int OCC, bool EDGE_IN, typename RLX, typename RLY,
@@ -352,6 +373,17 @@ template <typename T, int X, int Y, int Z> struct Nd2Auto {
     // the first stage reads runs of (X / first radix) points: straight from HBM when that is >= 128 bytes
     static constexpr bool EDGE_IN = HALF || (X > 1 && (X / RadixFirst<RLX>::value) * (int)sizeof(cplx<T>) >= 128);
 };
+
+// the complex32-storage twin of launch_nd2_auto's kernel: the same configuration (Nd2Auto<T, ...>)
+template <typename T, int X, int Y, int Z> static inline int launch_nd2_c32_auto(const TileArgs* a, hipStream_t s) {
+    using C = Nd2Auto<T, X, Y, Z>;
+    const long long tiles = (a->total + C::P - 1) / C::P;
+    if (tiles <= 0) return 0;
+    if (tiles > 2147483647ll) return -1;
+    hipLaunchKernelGGL((fft_nd2_kernel<Complex32<T>, X, Y, Z, C::P, C::NT, C::HALF, C::OCC, C::EDGE_IN, typename C::RLX,
+                                       typename C::RLY, typename C::RLZ>), dim3((unsigned)tiles), dim3(C::NT), 0, s, *a);
+    return (int)hipGetLastError();
+}
 
 template <typename T, int X, int Y, int Z> static inline int launch_nd2_auto(const TileArgs* a, hipStream_t s) {
     using C = Nd2Auto<T, X, Y, Z>;

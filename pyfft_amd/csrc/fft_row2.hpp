@@ -53,10 +53,13 @@ __device__ __forceinline__ int row2_pad(int i) { return i + (i >> 4); }
 // EPI (real-input rows, fft_real_row.hpp): a type whose EPI::run<NB, R, TPR, LR>(lds, v, a, tid, outb, valid) replaces the last stage's
 // stores -- it receives the transform in registers (v[b*R + k] = point b*TPR + k*LR + tid) and writes what it derives from it.  void:
 // the plain stores below, unchanged.
-template <typename T, int L, int TPR, int Ns, bool FIRST, bool HALF, typename RL, int LAY = 0, typename EPI = void> struct Row2Stages;
+// ST: storage type of the first stage's loads and the last stage's stores (fft_tile.hpp: widen / narrow); ST != T (complex32):
+// interleaved data, plain accesses -- the stages and exchanges are those of T.
+template <typename T, int L, int TPR, int Ns, bool FIRST, bool HALF, typename RL, int LAY = 0, typename EPI = void, typename ST = T>
+struct Row2Stages;
 
-template <typename T, int L, int TPR, int Ns, bool FIRST, bool HALF, int R, int... Rest, int LAY, typename EPI>
-struct Row2Stages<T, L, TPR, Ns, FIRST, HALF, RadixList<R, Rest...>, LAY, EPI> {
+template <typename T, int L, int TPR, int Ns, bool FIRST, bool HALF, int R, int... Rest, int LAY, typename EPI, typename ST>
+struct Row2Stages<T, L, TPR, Ns, FIRST, HALF, RadixList<R, Rest...>, LAY, EPI, ST> {
     static constexpr int NT = TPR;
     static constexpr int PPT = L / NT;
     static constexpr int NB = PPT / R;
@@ -110,9 +113,9 @@ struct Row2Stages<T, L, TPR, Ns, FIRST, HALF, RadixList<R, Rest...>, LAY, EPI> {
         static_assert(FIRST, "first-stage addressing");
         static_for<CNT>([&](auto ii) {
             constexpr int i = I0 + ii, b = i / R, k = i % R;
-            const cplx<T>* p = reinterpret_cast<const cplx<T>*>(inb + (size_t)(b * NT + k * LR) * sizeof(cplx<T>) + voff);
-            if constexpr (NTL) v[i] = __builtin_nontemporal_load(p);
-            else v[i] = *p;
+            const cplx<ST>* p = reinterpret_cast<const cplx<ST>*>(inb + (size_t)(b * NT + k * LR) * sizeof(cplx<ST>) + voff);
+            if constexpr (NTL) v[i] = widen<T, ST>(__builtin_nontemporal_load(p));
+            else v[i] = widen<T, ST>(*p);
         });
     }
 
@@ -220,6 +223,9 @@ struct Row2Stages<T, L, TPR, Ns, FIRST, HALF, RadixList<R, Rest...>, LAY, EPI> {
                                     *qr = p.x;
                                     *qi = p.y;
                                 }
+                            } else if constexpr (!std::is_same<T, ST>::value) {
+                                static_assert(NTS == 0, "complex32: plain stores only");
+                                *reinterpret_cast<cplx<ST>*>(outb + (size_t)(b * NT + k * Ns) * sizeof(cplx<ST>) + voff) = narrow<T, ST>(p);
                             } else {
                             char* kb = outb + (size_t)(b * NT + k * Ns) * sizeof(cplx<T>);
                             cplx<T>* q = reinterpret_cast<cplx<T>*>(kb + voff);
@@ -230,10 +236,11 @@ struct Row2Stages<T, L, TPR, Ns, FIRST, HALF, RadixList<R, Rest...>, LAY, EPI> {
                         });
                     });
                 };
-                if (a.nt & 4) stores(IC<2>{}); else if (a.nt & 2) stores(IC<1>{}); else stores(IC<0>{});
+                if constexpr (!std::is_same<T, ST>::value) stores(IC<0>{});
+                else if (a.nt & 4) stores(IC<2>{}); else if (a.nt & 2) stores(IC<1>{}); else stores(IC<0>{});
             }
         } else {
-            using Next = Row2Stages<T, L, TPR, Ns * R, false, HALF, RadixList<Rest...>, LAY, EPI>;
+            using Next = Row2Stages<T, L, TPR, Ns * R, false, HALF, RadixList<Rest...>, LAY, EPI, ST>;
             if constexpr (!FIRST) __syncthreads();  // everybody has fetched its operands of this stage
             if constexpr (!HALF) {
                 spill<0>(lds, v, tid);
@@ -261,8 +268,11 @@ struct Row2Stages<T, L, TPR, Ns, FIRST, HALF, RadixList<R, Rest...>, LAY, EPI> {
 };
 
 // OCC: waves per SIMD the register allocation must leave room for (1 = whatever the kernel needs)
-template <typename T, int L, int W, int NT, bool HALF, int OCC, typename RL, int LAY = 0>
+// TS = Complex32<T> (fft_tile.hpp): complex32 storage, interleaved (LAY 0), plain accesses
+template <typename TS, int L, int W, int NT, bool HALF, int OCC, typename RL, int LAY = 0>
 __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(OCC))) fft_row2_kernel(const TileArgs a) {
+    using T = typename StorageOf<TS>::work;
+    using ST = typename StorageOf<TS>::store;
     constexpr int TPR = NT / W;
     constexpr int PPT = L / TPR;
     constexpr int LP = L + L / 16;
@@ -274,12 +284,12 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(OCC))) 
     const bool valid = row < a.total;
     // (planes: the row's first real / imaginary scalar; the thread's offset below counts complex numbers' bytes and is halved at the access)
     const char* inb = (LAY & 1) ? reinterpret_cast<const char*>(reinterpret_cast<const T*>(a.in0) + row * a.ostride_in)
-                                : reinterpret_cast<const char*>(reinterpret_cast<const cplx<T>*>(a.in0) + row * a.ostride_in);
+                                : reinterpret_cast<const char*>(reinterpret_cast<const cplx<ST>*>(a.in0) + row * a.ostride_in);
     const char* inb1 = (LAY & 1) ? reinterpret_cast<const char*>(reinterpret_cast<const T*>(a.in1) + row * a.ostride_in) : nullptr;
     char* outb = (LAY & 2) ? reinterpret_cast<char*>(reinterpret_cast<T*>(a.out0) + row * a.ostride_out)
-                           : reinterpret_cast<char*>(reinterpret_cast<cplx<T>*>(a.out0) + row * a.ostride_out);
+                           : reinterpret_cast<char*>(reinterpret_cast<cplx<ST>*>(a.out0) + row * a.ostride_out);
     char* outb1 = (LAY & 2) ? reinterpret_cast<char*>(reinterpret_cast<T*>(a.out1) + row * a.ostride_out) : nullptr;
-    unsigned voff = (unsigned)u * (unsigned)sizeof(cplx<T>);
+    unsigned voff = (unsigned)u * (unsigned)sizeof(cplx<ST>);
     if constexpr (W > 1) {  // the row differs across the wave: fold the thread's offset into its own 64-bit base
         inb += (LAY & 1) ? voff / 2 : voff;
         if constexpr (LAY & 1) inb1 += voff / 2;
@@ -288,7 +298,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(OCC))) 
         voff = 0;
     }
     cplx<T> v[PPT];
-    Row2Stages<T, L, TPR, 1, true, HALF, RL, LAY>::run(lds + c * LP, v, a, u, inb, outb, voff, valid, nullptr, false, inb1, outb1);
+    Row2Stages<T, L, TPR, 1, true, HALF, RL, LAY, void, ST>::run(lds + c * LP, v, a, u, inb, outb, voff, valid, nullptr, false, inb1, outb1);
 }
 
 template <typename T, int L, int W, int NT, typename RL, bool HALF = false, int OCC = 1, int LAY = 0>

@@ -12,6 +12,7 @@
 //
 // The inverse transform is conj -> forward -> conj, folded into the load and the scaled store.
 #pragma once
+#include <type_traits>
 #include "fft_butterfly.hpp"
 #ifndef MIFFT_TREE_MIN_L
 #define MIFFT_TREE_MIN_L 64
@@ -42,6 +43,38 @@ struct TileArgs {
 };
 
 template <int... Rs> struct RadixList {};
+
+// Storage type ST of a kernel's HBM side: T (the default: memory holds cplx<T>, the working type) or _Float16 (complex32: one fp16
+// real and one fp16 imaginary part per point, docs/extensions.md "Half-precision transforms").  Only the first stage's loads and the
+// last stage's stores see ST: a load widens fp16 to T exactly, a store rounds T to fp16 once, to nearest even (fptrunc; not the
+// round-toward-zero v_cvt_pkrtz), +-inf beyond +-65504, NaN stays NaN.  For ST == T both are the identity.
+// A kernel template names its storage through its type parameter TS: T itself, or Complex32<T> (work in T, store complex32); the
+// kernels unpack it with StorageOf, so the existing instances keep their symbols and their code.
+template <typename T> struct Complex32 {};
+template <typename TS> struct StorageOf { using work = TS; using store = TS; };
+template <typename T> struct StorageOf<Complex32<T>> { using work = T; using store = _Float16; };
+template <typename T, typename ST> __device__ __forceinline__ cplx<T> widen(cplx<ST> p) {
+    if constexpr (std::is_same<T, ST>::value) return p;
+    else return __builtin_convertvector(p, cplx<T>);
+}
+template <typename T, typename ST> __device__ __forceinline__ cplx<ST> narrow(cplx<T> p) {
+    if constexpr (std::is_same<T, ST>::value) return p;
+    else return __builtin_convertvector(p, cplx<ST>);
+}
+// two consecutive complex32 points: one 8-byte access (the complex32 form of load_pair / store_pair, interleaved only)
+template <typename T, typename ST> __device__ __forceinline__ void load_pair_st(const void* base, long long g, cplx<T>* p) {
+    using V4 = ST __attribute__((ext_vector_type(4)));
+    const V4 t = *reinterpret_cast<const V4*>(reinterpret_cast<const cplx<ST>*>(base) + g);
+    p[0] = widen<T, ST>(t.xy);
+    p[1] = widen<T, ST>(t.zw);
+}
+template <typename T, typename ST> __device__ __forceinline__ void store_pair_st(void* base, long long g, const cplx<T>* p) {
+    using V4 = ST __attribute__((ext_vector_type(4)));
+    V4 t;
+    t.xy = narrow<T, ST>(p[0]);
+    t.zw = narrow<T, ST>(p[1]);
+    *reinterpret_cast<V4*>(reinterpret_cast<cplx<ST>*>(base) + g) = t;
+}
 
 // NT: non-temporal access (MIFFT_FLAG_STREAM_SRC / _DST: data read once / not re-read by the plan), interleaved only
 template <typename T, bool NT = false> __device__ __forceinline__ void load_pair(const TileArgs& a, long long g, cplx<T>& p0,
@@ -242,8 +275,12 @@ template <typename T, int L, int W, bool ROW, bool TR> struct LdsSize {
 };
 
 // ---------------------------------------------------------------------------------------------------
-template <typename T, int L, int W, int NT, bool ROW, bool TR, typename RL>
+// TS = Complex32<T>: complex32 storage (ROW tiles, interleaved data on both sides, plain accesses: the nt bits are ignored)
+template <typename TS, int L, int W, int NT, bool ROW, bool TR, typename RL>
 __global__ void __launch_bounds__(NT) fft_tile_kernel(const TileArgs a) {
+    using T = typename StorageOf<TS>::work;
+    using ST = typename StorageOf<TS>::store;
+    constexpr bool kST = !std::is_same<T, ST>::value;
     constexpr int P = L * W;
     constexpr int PPT = P / NT;
     static_assert(PPT * NT == P && PPT >= 2 && (PPT % 2) == 0, "bad tile configuration");
@@ -275,7 +312,12 @@ __global__ void __launch_bounds__(NT) fft_tile_kernel(const TileArgs a) {
             if constexpr (ROW) {
                 const int c = e / L, r = e % L;
                 const long long rr = col0 + c;
-                if (rr < a.total) load_vec<T, V, NTL>(a, rr * a.ostride_in + r, p);
+                if constexpr (kST) {
+                    static_assert(V == 2, "complex32: pairs only");
+                    if (rr < a.total) load_pair_st<T, ST>(a.in0, rr * a.ostride_in + r, p);
+                } else {
+                    if (rr < a.total) load_vec<T, V, NTL>(a, rr * a.ostride_in + r, p);
+                }
             } else {
                 const int r = e / W, c = e % W;
                 const long long cc = col0 + c;
@@ -304,7 +346,9 @@ __global__ void __launch_bounds__(NT) fft_tile_kernel(const TileArgs a) {
         });
     };
     // (streaming hint only on the plain interleaved path)
-    if constexpr (kQuadShape) {
+    if constexpr (kST) {
+        load_phase(IC<2>{}, IC<0>{});
+    } else if constexpr (kQuadShape) {
         if (quad_in) load_phase(IC<4>{}, IC<0>{});
         else if (a.nt & 1) load_phase(IC<2>{}, IC<1>{});
         else load_phase(IC<2>{}, IC<0>{});
@@ -353,12 +397,19 @@ __global__ void __launch_bounds__(NT) fft_tile_kernel(const TileArgs a) {
                 static_for<V>([&](auto k) { p[k] = lds[lds_addr<L, W, ROW>(q, c + k)]; });
             }
             static_for<V>([&](auto k) { p[k].x *= sx; p[k].y *= sy; });
-            if (valid) store_vec<T, V, NTS>(a, g, p);
+            if constexpr (kST) {
+                static_assert(V == 2 && NTS == 0, "complex32: plain pairs only");
+                if (valid) store_pair_st<T, ST>(a.out0, g, p);
+            } else {
+                if (valid) store_vec<T, V, NTS>(a, g, p);
+            }
         });
     };
     // fp64, interleaved output, write-through: point by point, so that a store instruction covers whole lines (store_vec, V == 1)
     constexpr bool kPointWise = sizeof(cplx<T>) == 16;
-    if constexpr (kQuadShape) {
+    if constexpr (kST) {
+        store_phase(IC<2>{}, IC<0>{});
+    } else if constexpr (kQuadShape) {
         // (planes in small launches: write-through 16-byte stores, second batch of round 4; fp64 planes: PAIRS -- four doubles are 32 bytes
         // per lane and plane, the fragmenting form again: fp64 planes N = 512 at 32 MiB 0.47 written through in fours, 0.51 plain)
         if (quad_out && (a.nt & 4) && !kPointWise) store_phase(IC<4>{}, IC<2>{});

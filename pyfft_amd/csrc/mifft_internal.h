@@ -71,6 +71,11 @@ int mifft_real_row_dispatch_f32(int L, int inverse, const mifft::TileArgs* a, hi
 int mifft_real_row_dispatch_f64(int L, int inverse, const mifft::TileArgs* a, hipStream_t s, int query_only);
 // fft_nd2z.hip: 0 = launched (query 1: a kernel exists; query 2: one that is preferred at every buffer size), -2 = none, -1 = grid too large
 int mifft_nd2z(int f64, int x, int y, int z, const mifft::TileArgs* a, hipStream_t s, int query);
+// fft_half.hip / fft_nd2_c32_*.hip: complex32 twins of the fp32 one-launch kernels; 0 launched (query: a kernel exists), -2 none, -1 grid too large
+int mifft_c32_row_dispatch(int L, const mifft::TileArgs* a, hipStream_t s, int query_only);
+int mifft_c32_nd_launch(long long n, const mifft::NdArgs* a, hipStream_t s);
+int mifft_nd2_c32_supported(int x, int y, int z);
+int mifft_nd2_c32_launch(int x, int y, int z, const mifft::TileArgs* a, hipStream_t s);
 }
 
 namespace mifft {

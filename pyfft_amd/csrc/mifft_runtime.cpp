@@ -188,6 +188,30 @@ bool nd2z_preferred(bool f64, int x, int y, int z, bool small_launch) {
     return g_debug[MIFFT_DEBUG_ALT_ROWS] != 6 && mifft_nd2z(f64 ? 1 : 0, x, y, z, nullptr, nullptr, small_launch ? 1 : 2) == 0;
 }
 
+// the stage list of the run-time-shaped N-D kernel (fft_nd.hpp) for the axes dims (x, y, z): axis geometry, radices, nstages;
+// -1 if it needs more than kNdMaxStages stages
+int nd_stage_list(const long long dims[3], bool f64, mifft::NdArgs* a) {
+    int logs = 0, ns = 0;
+    for (int ax = 0; ax < 3; ++ax) {
+        a->logL[ax] = ilog2(dims[ax]);
+        a->logS[ax] = logs;
+        logs += a->logL[ax];
+        int rad[16];
+        const int nr = nd_radices((int)dims[ax], f64 ? 8 : 16, rad);
+        int logNs = 0;
+        for (int i = 0; i < nr; ++i) {
+            if (ns >= mifft::kNdMaxStages) return -1;
+            a->st_axis[ns] = (unsigned char)ax;
+            a->st_radix[ns] = (unsigned char)rad[i];
+            a->st_logNs[ns] = (unsigned char)logNs;
+            logNs += ilog2(rad[i]);
+            ++ns;
+        }
+    }
+    a->nstages = ns;
+    return 0;
+}
+
 int launch_nd(const mifft_pass* p, const void* in0, const void* in1, void* out0, void* out1, hipStream_t s) {
     // fixed-shape kernels (fft_nd2.hpp) for the common shapes, interleaved on both sides
     // the run-time-shaped kernel only: the development switch, or variant 1 of the pass (the plan asks for it where that kernel measured
@@ -325,24 +349,8 @@ int launch_nd(const mifft_pass* p, const void* in0, const void* in1, void* out0,
     const long long dims[3] = {p->L, p->M, p->S};
     a.total = p->outer * dims[0] * dims[1] * dims[2];
     const bool f64 = p->precision == MIFFT_F64;
-    int logs = 0, ns = 0;
-    for (int ax = 0; ax < 3; ++ax) {
-        a.logL[ax] = ilog2(dims[ax]);
-        a.logS[ax] = logs;
-        logs += a.logL[ax];
-        int rad[16];
-        const int nr = nd_radices((int)dims[ax], f64 ? 8 : 16, rad);
-        int logNs = 0;
-        for (int i = 0; i < nr; ++i) {
-            if (ns >= mifft::kNdMaxStages) return set_err(MIFFT_E_UNSUPPORTED, "ND pass: too many stages");
-            a.st_axis[ns] = (unsigned char)ax;
-            a.st_radix[ns] = (unsigned char)rad[i];
-            a.st_logNs[ns] = (unsigned char)logNs;
-            logNs += ilog2(rad[i]);
-            ++ns;
-        }
-    }
-    a.nstages = ns;
+    if (nd_stage_list(dims, f64, &a) != 0) return set_err(MIFFT_E_UNSUPPORTED, "ND pass: too many stages");
+    const int ns = a.nstages;
     a.split = (p->layout == MIFFT_SPLIT && !(p->flags & MIFFT_FLAG_SRC_INTERLEAVED)) ? 1 : 0;
     a.split_out = (p->layout == MIFFT_SPLIT && !(p->flags & MIFFT_FLAG_DST_INTERLEAVED)) ? 1 : 0;
     a.inverse = p->inverse ? 1 : 0;
@@ -1384,6 +1392,91 @@ int mifft_launch_real_row(int32_t precision, int32_t n, int32_t inverse, int64_t
     const int rc = precision == MIFFT_F64 ? mifft_real_row_dispatch_f64((int)L, inverse, &a, (hipStream_t)stream, 0)
                                           : mifft_real_row_dispatch_f32((int)L, inverse, &a, (hipStream_t)stream, 0);
     if (rc == -2) return set_err(MIFFT_E_UNSUPPORTED, "real row: no kernel for n = %d", n);
+    if (rc == -1) return set_err(MIFFT_E_INVALID, "grid too large");
+    if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
+    return 0;
+}
+// complex32 transforms: the one-launch shape set of interleaved fp32 data (1-D rows up to 32768 points, the N-D shapes of
+// mifft_nd_shape_supported with MIFFT_VARIANT_INTERLEAVED_ONLY), unit axes taken as given
+int mifft_half_supported(int32_t x, int32_t y, int32_t z) {
+    if (x < 1 || y < 1 || z < 1 || !is_pow2(x) || !is_pow2(y) || !is_pow2(z)) return MIFFT_E_UNSUPPORTED;
+    if (y == 1 && z == 1) return (x >= 2 && mifft_c32_row_dispatch(x, nullptr, nullptr, 1) == 0) ? 0 : MIFFT_E_UNSUPPORTED;
+    return mifft_nd_shape_supported(MIFFT_F32, x, y, z, MIFFT_VARIANT_INTERLEAVED_ONLY) == 0 ? 0 : MIFFT_E_UNSUPPORTED;
+}
+// the kernel family a supported shape runs (after dropping its unit axes): the ROW tile, the register-edged row, the fixed-shape N-D
+// kernel or the run-time-shaped one (variant 1: the latter wherever it takes the shape, as variant 1 of an fp32 ND pass)
+int mifft_half_kernel(int32_t x, int32_t y, int32_t z, int32_t variant) {
+    if (mifft_half_supported(x, y, z) != 0 || (variant != 0 && variant != 1)) return MIFFT_E_UNSUPPORTED;
+    int d[3] = {1, 1, 1}, nd = 0;
+    for (int v : {x, y, z})
+        if (v > 1) d[nd++] = v;
+    if (nd <= 1) return d[0] >= 256 ? MIFFT_HALF_KERNEL_ROW : MIFFT_HALF_KERNEL_TILE;
+    if (variant == 1 && (long long)d[0] * d[1] * d[2] <= mifft_nd_max_points(0)) return MIFFT_HALF_KERNEL_ND;
+    return mifft_nd2_c32_supported(d[0], d[1], d[2]) == 0 ? MIFFT_HALF_KERNEL_ND2 : MIFFT_HALF_KERNEL_ND;
+}
+int mifft_launch_half(int32_t x, int32_t y, int32_t z, int32_t variant, int32_t inverse, int64_t transforms, const void* in, void* out, const void* tw_x,
+                      const void* tw_y, const void* tw_z, double scale, mifft_stream_t stream) {
+    if (x < 1 || y < 1 || z < 1 || !is_pow2(x) || !is_pow2(y) || !is_pow2(z))
+        return set_err(MIFFT_E_INVALID, "half: shape %d x %d x %d is not powers of two", z, y, x);
+    if (variant != 0 && variant != 1) return set_err(MIFFT_E_INVALID, "half: variant must be 0 or 1");
+    const int kind = mifft_half_kernel(x, y, z, variant);
+    if (kind < 0) return set_err(MIFFT_E_UNSUPPORTED, "half: no one-launch kernel for %d x %d x %d", z, y, x);
+    if (inverse != 0 && inverse != 1) return set_err(MIFFT_E_INVALID, "half: inverse must be 0 or 1");
+    if (transforms < 0) return set_err(MIFFT_E_INVALID, "half: negative transform count");
+    if (!in || !out) return set_err(MIFFT_E_INVALID, "half: null buffer");
+    // unit axes dropped: the data of (x, 1, z) is that of (x, z, 1); every remaining axis needs its table
+    long long d[3] = {1, 1, 1};
+    const void* tw[3] = {nullptr, nullptr, nullptr};
+    int nd = 0;
+    const int32_t dims_in[3] = {x, y, z};
+    const void* tw_in[3] = {tw_x, tw_y, tw_z};
+    for (int ax = 0; ax < 3; ++ax)
+        if (dims_in[ax] > 1) {
+            if (!tw_in[ax]) return set_err(MIFFT_E_INVALID, "half: null twiddle table for an axis of %d points", dims_in[ax]);
+            d[nd] = dims_in[ax];
+            tw[nd++] = tw_in[ax];
+        }
+    if (((uintptr_t)in | (uintptr_t)out) & 15) return set_err(MIFFT_E_INVALID, "half: buffers must be 16-byte aligned");
+    if (((uintptr_t)tw[0] | (uintptr_t)tw[1] | (uintptr_t)tw[2]) & 7) return set_err(MIFFT_E_INVALID, "half: tables must be 8-byte aligned");
+    const long long n = d[0] * d[1] * d[2];
+    if (mul3_checked(transforms, n, 4) < 0) return set_err(MIFFT_E_INVALID, "half: transforms * points overflows");
+    if (transforms == 0) return 0;
+    const uintptr_t bytes = (uintptr_t)(transforms * n * 4);
+    const uintptr_t i0 = (uintptr_t)in, o0 = (uintptr_t)out;
+    if (i0 != o0 && i0 < o0 + bytes && o0 < i0 + bytes)
+        return set_err(MIFFT_E_INVALID, "half: input and output overlap (in place is exact aliasing only)");
+    hipStream_t s = (hipStream_t)stream;
+    int rc;
+    if (kind == MIFFT_HALF_KERNEL_ND) {
+        mifft::NdArgs a;
+        memset(&a, 0, sizeof(a));
+        a.in0 = in; a.out0 = out;
+        a.tw[0] = tw[0]; a.tw[1] = tw[1]; a.tw[2] = tw[2];
+        a.total = transforms * n;
+        if (nd_stage_list(d, false, &a) != 0) return set_err(MIFFT_E_UNSUPPORTED, "half: too many stages");
+        a.inverse = inverse;
+        a.scale = scale;
+        // the register edge of the fp32 twin (launch_nd): the last stage writes runs of >= 16 points straight to HBM
+        const int axn = a.st_axis[a.nstages - 1];
+        a.edge_out = (((d[axn] / a.st_radix[a.nstages - 1]) << a.logS[axn]) * 8 >= 128) ? 1 : 0;
+        rc = mifft_c32_nd_launch(n, &a, s);
+    } else {
+        mifft::TileArgs a;
+        memset(&a, 0, sizeof(a));
+        a.in0 = in; a.out0 = out;
+        a.tw_L = tw[0]; a.tw_lo = tw[1]; a.tw_hi = tw[2];
+        a.inverse = inverse;
+        a.scale = scale;
+        if (kind == MIFFT_HALF_KERNEL_ND2) {
+            a.total = transforms * n;                        // points
+            rc = mifft_nd2_c32_launch((int)d[0], (int)d[1], (int)d[2], &a, s);
+        } else {
+            a.total = transforms;                            // rows
+            a.ostride_in = a.ostride_out = n;
+            rc = mifft_c32_row_dispatch((int)n, &a, s, 0);
+        }
+    }
+    if (rc == -2) return set_err(MIFFT_E_UNSUPPORTED, "half: no kernel for %d x %d x %d", z, y, x);
     if (rc == -1) return set_err(MIFFT_E_INVALID, "grid too large");
     if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
     return 0;

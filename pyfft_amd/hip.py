@@ -589,6 +589,8 @@ def Plan(*args, **kwds):
     `mempool`: any object with an allocate(nbytes) method returning a buffer-like object.
     `real=True`: real-input transforms (pyfft_amd/real.py): `dtype` float32 / float64 (or complex64 / complex128) names the precision,
     execute(real_in, spectrum_out) / execute(spectrum_in, real_out, inverse=True), out of place, numpy's rfftn / irfftn layout.
+    `dtype="complex32"` (or torch.complex32): half-precision transforms (pyfft_amd/half.py): interleaved fp16 data, fp32 arithmetic, one
+    rounding to fp16 at the store; the one-launch shapes of complex64 only.  numpy.float16 (split half planes) is a ValueError.
     `parent_shape=`, `any_size=True`: opt-in extensions (tiles of a bigger array; sizes that are not powers of two), see
     pyfft_amd/generic.py.  Without them a size that is not a power of two is a ValueError, as in the reference.
     `fast_math`: accepted for signature parity and ignored -- the reference passes -use_fast_math to nvcc for its on-device
@@ -605,6 +607,15 @@ def Plan(*args, **kwds):
     real = bool(kwds.pop('real', False))
     if real and (parent_shape is not None or any_size):
         raise ValueError("pyfft_amd: real=True cannot be combined with any_size= or parent_shape=")
+    # complex32 (pyfft_amd/half.py): routed before FFTPlan.validate, which knows no half dtype
+    from .half import HalfFFTPlan, is_complex32, is_float16
+    dtype = args[1] if len(args) > 1 else kwds.get('dtype')
+    half = is_complex32(dtype)
+    if is_float16(dtype) and not real and parent_shape is None and not any_size:
+        raise ValueError("pyfft_amd: float16 would mean split half planes, which do not exist: only interleaved complex32 "
+                         "(dtype=\"complex32\" or torch.complex32) has half-precision transforms")
+    if half and (real or parent_shape is not None or any_size):
+        raise ValueError("pyfft_amd: dtype=complex32 cannot be combined with real=, any_size= or parent_shape=")
     generic = (parent_shape is not None or any_size) and not real
     if generic and parent_shape is None:
         # any_size=True on a power-of-two shape: the dense plan itself (no work array, no gather / scatter)
@@ -616,7 +627,9 @@ def Plan(*args, **kwds):
             pass
 
     # argument errors first (ValueError, as in the reference), then the device
-    if real:
+    if half:
+        HalfFFTPlan.validate(*args, **kwds)
+    elif real:
         from .real import RealFFTPlan
         RealFFTPlan.validate(*args, **kwds)
     elif not generic:
@@ -646,6 +659,8 @@ def Plan(*args, **kwds):
     context = Context(device, stream_obj, mempool)
     prev = context.activate()       # context=i: tables and scratch are allocated on device i
     try:
+        if half:
+            return HalfFFTPlan(context, *args, **kwds)
         if real:
             return RealFFTPlan(context, *args, **kwds)
         if generic:
