@@ -426,6 +426,10 @@ int mifft_aux_count_mismatch(const void *a, const void *b, size_t nbytes, uint64
  *   mifft_mixed_supported  0 if rows of n points have such a kernel, else MIFFT_E_UNSUPPORTED
  */
 int mifft_mixed_supported(int32_t precision, int32_t n);
+/* The radix list the mixed-radix kernels run for a smooth length n (2 <= n <= 2^24), in stage order: host only, no device needed.
+ * Returns the number of stages (at most MIFFT_MIXED_MAX_STAGES, written to radix[0 ..]) or MIFFT_E_UNSUPPORTED (n not smooth). */
+#define MIFFT_MIXED_MAX_STAGES 12
+int mifft_mixed_radices(int32_t precision, int32_t n, int32_t *radix);
 int mifft_launch_mixed_rows(int32_t precision, int32_t n, int64_t rows, int64_t stride_in, int64_t stride_out, const void *in,
                             void *out, const void *tw, int32_t inverse, double scale, mifft_stream_t stream);
 /* The same transform along ANY axis of a dense array viewed as [outer][n][inner] (inner = product of the faster axes; inner == 1

@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmifft.so")
 
 ABI_VERSION = 6
+MIFFT_MIXED_MAX_STAGES = 12       # (include/mifft.h: the length of mifft_mixed_radices' list)
 
 E_INVALID = -1
 E_UNSUPPORTED = -2
@@ -215,6 +216,7 @@ PROTOTYPES = {
     "mifft_aux_mul_rows": (ctypes.c_int, [_i32, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _vp]),
     "mifft_aux_count_mismatch": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp, _vp]),
     "mifft_mixed_supported": (ctypes.c_int, [_i32, _i32]),
+    "mifft_mixed_radices": (ctypes.c_int, [_i32, _i32, ctypes.POINTER(ctypes.c_int32)]),
     "mifft_launch_mixed_rows": (ctypes.c_int, [_i32, _i32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _vp, _i32,
                                                 ctypes.c_double, _vp]),
     "mifft_launch_mixed_lines": (ctypes.c_int, [_i32, _i32, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _vp, _i32, _i32, ctypes.c_double, _vp]),

@@ -197,6 +197,15 @@ extern "C" int mifft_mixed_supported_impl(int f64, int n) {
     return factor(n, radix) ? 0 : -2;
 }
 
+// the radix list of factor_search, in stage order (the count; 0 if n is not smooth)
+extern "C" int mifft_mixed_radices_impl(int n, int32_t* radix) {
+    static_assert(kMaxStages == MIFFT_MIXED_MAX_STAGES, "radix list length");
+    int r[kMaxStages];
+    const int ns = factor(n, r);
+    for (int i = 0; i < ns; ++i) radix[i] = r[i];
+    return ns;
+}
+
 namespace {
 
 // lines per tile: the largest W <= cap / n that divides `inner` (a tile's W lines are adjacent and share one o); the full tile when

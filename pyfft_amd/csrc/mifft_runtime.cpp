@@ -1212,6 +1212,14 @@ int mifft_mixed_supported(int32_t precision, int32_t n) {
     return mifft_mixed_supported_impl(precision == MIFFT_F64, n) == 0 ? 0 : MIFFT_E_UNSUPPORTED;
 }
 
+int mifft_mixed_radices(int32_t precision, int32_t n, int32_t* radix) {
+    if (precision != MIFFT_F32 && precision != MIFFT_F64) return MIFFT_E_UNSUPPORTED;
+    if (!radix) return set_err(MIFFT_E_INVALID, "mixed radices: null result pointer");
+    if (n < 2 || n > (1 << 24)) return MIFFT_E_UNSUPPORTED;
+    const int ns = mifft_mixed_radices_impl(n, radix);
+    return ns > 0 ? ns : MIFFT_E_UNSUPPORTED;
+}
+
 int mifft_launch_mixed_rows(int32_t precision, int32_t n, int64_t rows, int64_t stride_in, int64_t stride_out, const void* in, void* out,
                             const void* tw, int32_t inverse, double scale, mifft_stream_t stream) {
     if (mifft_mixed_supported(precision, n) != 0) return set_err(MIFFT_E_UNSUPPORTED, "mixed rows: no kernel for n = %d", n);

@@ -15,9 +15,9 @@ streaming helper kernels of the C ABI (`mifft_aux_copy`, `mifft_aux_mul_rows`):
               * a SMOOTH length n = 2^a 3^b 5^c 7^d up to 4096 (fp32) / 2048 (fp64): the lines gathered into dense rows, ONE
                 mixed-radix launch (csrc/fft_mixed.hip: radix-3 / 5 / 7 butterflies next to the power-of-two ones), scattered back
               * any other length n: Bluestein -- rows a[j] = x[j] * c[j] zero-padded to m = 2^k >= 2n - 1 with the chirp
-                c[j] = exp(-i pi j^2 / n), A = FFT_m(a), A *= FFT_m(b) (b = conj chirp, wrapped, evaluated on the host in
-                float64; its spectrum is computed ONCE, when the plan is built, by this engine's own float64 kernels on the
-                device: _device_fft), y = IFFT_m(A), X[k] = y[k] * c[k]
+                c[j] = exp(-i pi j^2 / n), A = FFT_m(a), A *= FFT_m(b) (b = conj chirp, wrapped; chirp and spectrum computed
+                ONCE, when the plan is built, on the host in extended precision and rounded once: _bluestein_spectrum),
+                y = IFFT_m(A), X[k] = y[k] * c[k]
     scatter  work array -> user output, with the plan's scale rule (kernel.py:23-37) and the conjugation trick for the
              inverse transform
 
@@ -38,12 +38,74 @@ def _is_pow2(n):
     return n >= 1 and (n & (n - 1)) == 0
 
 
-def _chirp(n, complex_dtype):
-    """c[j] = exp(-i*pi*j^2/n), j < n, with the phase reduced exactly (j^2 mod 2n) and evaluated in float64"""
+# pi in extended precision (numpy.pi is the float64 one: 1.2e-16 short, which an extended-precision angle would keep)
+_PI_LD = numpy.longdouble("3.14159265358979323846264338327950288")
+
+
+def _chirp_ld(n):
+    """c[j] = exp(-i*pi*j^2/n), j < n, with the phase reduced exactly (j^2 mod 2n) and evaluated in extended precision (clongdouble)"""
     j = numpy.arange(n, dtype=numpy.int64)
     ph = (j * j) % (2 * n)
-    ang = -numpy.pi * ph.astype(numpy.float64) / float(n)
-    return (numpy.cos(ang) + 1j * numpy.sin(ang))
+    ang = -_PI_LD * ph.astype(numpy.longdouble) / numpy.longdouble(n)
+    return numpy.cos(ang) + 1j * numpy.sin(ang)
+
+
+def _chirp(n, complex_dtype=numpy.complex128):
+    """the chirp as complex128, rounded once from extended precision (the caller rounds it to the working precision: at most one more
+    rounding, none for fp64 plans)"""
+    return _chirp_ld(n).astype(numpy.complex128)
+
+
+def _bluestein_spectrum(n, m):
+    """FFT_m(b) of Bluestein's wrapped conjugate chirp (b[j] = conj(c[j]) for j < n, b[m - j] = b[j], zero between) as complex128: the
+    chirp and the transform in extended precision on the host, rounded once.  (Evaluated in float64 -- the chirp by float64 cos / sin,
+    the transform by this engine's float64 kernels -- the table carried a few units of float64 rounding into every fp64 result: the
+    fp64 Bluestein model of tests/test_accuracy_model.py then had half the headroom to the accuracy bound.)"""
+    c = _chirp_ld(n)
+    b = numpy.zeros(m, numpy.clongdouble)
+    b[:n] = numpy.conj(c)
+    b[m - n + 1:] = numpy.conj(c[1:][::-1])
+    return _fft_ld(b).astype(numpy.complex128)
+
+
+def _fft_ld(x):
+    """DFT of a smooth-length vector in extended precision (clongdouble) on the host: the stage algebra of csrc/fft_mixed.hip with
+    prime radices (4 for pairs of 2s), each stage's DFT written out over its operands.  Plan-build-time tables only."""
+    x = numpy.asarray(x, numpy.clongdouble)
+    n = x.size
+    radices, r = [], n
+    for p in (4, 2, 3, 5, 7):
+        while r % p == 0:
+            radices.append(p)
+            r //= p
+    assert r == 1, "not a smooth length: %d" % n
+    t = numpy.arange(n, dtype=numpy.int64)
+    ang = -2 * _PI_LD * t.astype(numpy.longdouble) / numpy.longdouble(n)
+    w = numpy.cos(ang) + 1j * numpy.sin(ang)                 # w(n)^t, t < n
+    Ns = 1
+    for p in radices:
+        L = n // p
+        jb = numpy.arange(L, dtype=numpy.int64)
+        jm = jb % Ns
+        v = [x[k * L:(k + 1) * L] * w[(k * jm * (L // Ns)) % n] for k in range(p)]
+        q0 = (jb - jm) * p + jm
+        y = numpy.empty_like(x)
+        for q in range(p):
+            acc = v[0].copy()
+            for k in range(1, p):
+                acc += v[k] * w[(q * k * L) % n]
+            y[q0 + q * Ns] = acc
+        x = y
+        Ns *= p
+    return x
+
+
+def _unit_roots(count, step, period):
+    """w(period)^(k * step) = exp(-2 pi i k step / period), k < count, as complex128 rounded once from extended precision (every table
+    of the mixed-radix and Bluestein kernels: the caller rounds it to the working precision)"""
+    k = (numpy.arange(count, dtype=numpy.int64) * int(step)) % int(period)
+    ang = -2 * _PI_LD * k.astype(numpy.longdouble) / numpy.longdouble(period)
+    return (numpy.cos(ang) + 1j * numpy.sin(ang)).astype(numpy.complex128)
 
 
 class _Axis(object):
@@ -161,9 +223,7 @@ class GenericFFTPlan(object):
             ax.blue = None
             if not ax.pow2 and N.lib.mifft_mixed_supported(self._precision, n) == 0:
                 # smooth length (2^a 3^b 5^c 7^d): ONE mixed-radix launch on the dense rows instead of Bluestein's three transforms
-                k = numpy.arange(n, dtype=numpy.float64)
-                ang = -2.0 * numpy.pi * k / float(n)
-                ax.mixed_tw = self._upload((numpy.cos(ang) + 1j * numpy.sin(ang)).astype(self._cdtype))
+                ax.mixed_tw = self._upload(_unit_roots(n, 1, n).astype(self._cdtype))
                 ax.m, ax.plan, ax.chirp, ax.bhat = n, None, None, None
                 self._axes.append(ax)
                 continue
@@ -181,14 +241,8 @@ class GenericFFTPlan(object):
                 # any other length whose padded rows fit a tile: Bluestein's algorithm in ONE launch (both m-point transforms
                 # inside LDS, csrc/fft_mixed.hip) instead of three batched transforms and four streaming copies
                 m = mb.value
-                c = _chirp(n, self._cdtype)
-                b = numpy.zeros(m, numpy.complex128)
-                b[:n] = numpy.conj(c)
-                b[m - n + 1:] = numpy.conj(c[1:][::-1])
-                k = numpy.arange(m, dtype=numpy.float64)
-                ang = -2.0 * numpy.pi * k / float(m)
-                ax.blue = (m, self._upload((numpy.cos(ang) + 1j * numpy.sin(ang)).astype(self._cdtype)),
-                           self._upload(c.astype(self._cdtype)), self._upload((self._device_fft(b) / m).astype(self._cdtype)))
+                ax.blue = (m, self._upload(_unit_roots(m, 1, m).astype(self._cdtype)),
+                           self._upload(_chirp(n).astype(self._cdtype)), self._upload((_bluestein_spectrum(n, m) / m).astype(self._cdtype)))
                 ax.m, ax.plan, ax.chirp, ax.bhat = n, None, None, None
                 self._axes.append(ax)
                 continue
@@ -196,12 +250,8 @@ class GenericFFTPlan(object):
             ax.plan = None                    # a batched ROW plan of ax.m points, built below if the work-array path runs
             ax.chirp = ax.bhat = None
             if not ax.pow2 and not self._tiled:
-                c = _chirp(n, self._cdtype)
-                b = numpy.zeros(ax.m, numpy.complex128)
-                b[:n] = numpy.conj(c)
-                b[ax.m - n + 1:] = numpy.conj(c[1:][::-1])
-                ax.chirp = self._upload(c.astype(self._cdtype))
-                ax.bhat = self._upload(self._device_fft(b).astype(self._cdtype))
+                ax.chirp = self._upload(_chirp(n).astype(self._cdtype))
+                ax.bhat = self._upload(_bluestein_spectrum(n, ax.m).astype(self._cdtype))
             self._axes.append(ax)
         # 1-D smooth length, interleaved, dense: the mixed-radix launch reads the user's input and writes the user's output itself
         # (conjugation of the inverse direction and the scale included): one HBM round trip, no work array
@@ -225,9 +275,7 @@ class GenericFFTPlan(object):
                 elif ax.mixed_tw is not None:
                     tabs.append(ax.mixed_tw)
                 else:
-                    k = numpy.arange(ax.n, dtype=numpy.float64)
-                    ang = -2.0 * numpy.pi * k / float(ax.n)
-                    tabs.append(self._upload((numpy.cos(ang) + 1j * numpy.sin(ang)).astype(self._cdtype)))
+                    tabs.append(self._upload(_unit_roots(ax.n, 1, ax.n).astype(self._cdtype)))
             self._direct_nd = tabs
             # ... and the whole transform in ONE launch when it fits a work-group's LDS (csrc/fft_mixed_nd.hip, round 4): (100, 100)
             # is 80 KB; one HBM round trip instead of one per axis
@@ -263,55 +311,6 @@ class GenericFFTPlan(object):
         if m not in self._rowplans:
             self._rowplans[m] = FFTPlan(self._sub, (m,), dtype=self._cdtype, normalize=True, wait_for_finish=False)
         return self._rowplans[m]
-
-    def _device_fft(self, b):
-        """FFT_m of the host vector `b` (complex128) computed ON THE DEVICE by this engine's own float64 kernels, returned as a
-        host complex128 array: the spectrum of Bluestein's wrapped conjugate chirp, a plan-build-time constant (an FFT engine
-        transforms its own chirp; the reference lists non-power-of-two sizes as a TODO, TODO.txt:8).  Always float64, also for
-        fp32 plans, so that the table is rounded ONCE to the working precision like every other table of the engine
-        (plan._twiddle_table).  m a power of two: a dense FFTPlan of m points; m smooth: the mixed-radix row kernel, or the
-        two-launch long form beyond its tile (include/mifft.h: mifft_launch_mixed_rows / mifft_launch_mixed_long)."""
-        ctx = self._context
-        cd = numpy.dtype(numpy.complex128)
-        host = numpy.ascontiguousarray(b, dtype=cd)
-        m = int(host.shape[0])
-        stream = ctx.stream_handle()
-        keep = []
-
-        def dev(arr):
-            arr = numpy.ascontiguousarray(arr)
-            mem = ctx.allocate_raw(arr.nbytes)
-            ctx.upload(mem, arr)
-            keep.append(mem)
-            return ctx.pointer_of(mem)
-
-        def roots(count, step, period):
-            k = numpy.arange(count, dtype=numpy.float64) * float(step)
-            ang = -2.0 * numpy.pi * numpy.fmod(k, float(period)) / float(period)
-            return dev((numpy.cos(ang) + 1j * numpy.sin(ang)).astype(cd))
-
-        src = dev(host)
-        dst = src
-        if _is_pow2(m):
-            plan = FFTPlan(self._sub, (m,), dtype=cd, normalize=False, wait_for_finish=True)
-            plan.execute(src)
-            plan.close()
-        elif N.lib.mifft_mixed_supported(N.F64, m) == 0:
-            N.check(N.lib.mifft_launch_mixed_rows(N.F64, m, 1, m, m, src, src, roots(m, 1, m), 0, 1.0, stream), "mifft_launch_mixed_rows")
-        else:
-            n1, n2 = ctypes.c_int32(0), ctypes.c_int32(0)
-            N.check(N.lib.mifft_mixed_long_split(N.F64, m, ctypes.byref(n1), ctypes.byref(n2)), "mifft_mixed_long_split(%d)" % m)
-            shift = max(1, (int(m - 1).bit_length() + 1) // 2)
-            dst = dev(numpy.zeros(m, cd))
-            N.check(N.lib.mifft_launch_mixed_long(N.F64, n1.value, n2.value, 1, src, dst, dst, roots(n1.value, 1, n1.value),
-                                                  roots(n2.value, 1, n2.value), roots(1 << shift, 1, m),
-                                                  roots(((m - 1) >> shift) + 1, 1 << shift, m), shift, 0, 1.0, stream),
-                    "mifft_launch_mixed_long")
-        out = numpy.empty(m, cd)
-        N.check(N.lib.mifft_memcpy_d2h(out.ctypes.data, dst, out.nbytes, stream), "mifft_memcpy_d2h")
-        N.check(N.lib.mifft_stream_sync(stream), "mifft_stream_sync")
-        del keep[:]
-        return out
 
     def _upload(self, host):
         host = numpy.ascontiguousarray(host)
@@ -350,9 +349,7 @@ class GenericFFTPlan(object):
         """(n1, n2, w(n1)^m, w(n2)^m, lo, hi, shift) for mifft_launch_mixed_long: w(n)^e = lo[e & (2^shift - 1)] * hi[e >> shift],
         every entry evaluated in float64."""
         def roots(count, step, period):
-            k = numpy.arange(count, dtype=numpy.float64) * float(step)
-            ang = -2.0 * numpy.pi * numpy.fmod(k, float(period)) / float(period)
-            return self._upload((numpy.cos(ang) + 1j * numpy.sin(ang)).astype(self._cdtype))
+            return self._upload(_unit_roots(count, step, period).astype(self._cdtype))
         shift = max(1, (int(n - 1).bit_length() + 1) // 2)
         lo = roots(1 << shift, 1, n)
         hi = roots(((n - 1) >> shift) + 1, 1 << shift, n)

@@ -4,6 +4,8 @@ HipContext mirrors helpers.CudaContext (test/helpers.py:29-74): allocate / toGpu
 getPlan / timers / supportsDouble.  Data generation and the error metric come from the oracle
 (oracle/pyfft_oracle.py), which only tests may import.
 """
+import ctypes
+
 import numpy
 
 COMPLEX_DTYPES = [numpy.complex64, numpy.complex128]
@@ -170,17 +172,59 @@ def unit_roundoff(dtype):
     return 2.0 ** -53 if numpy.dtype(dtype) in (numpy.dtype(numpy.complex128), numpy.dtype(numpy.float64)) else 2.0 ** -24
 
 
-def accuracy_bound(dtype, n_points):
+def bound_levels(n_points):
+    """L = ceil(log2(n_points)): log2 for a power of two"""
+    return (int(n_points) - 1).bit_length()
+
+
+def accuracy_bound(dtype, n_points, levels=None):
     """(L1-relative, max|err| / rms(ref)) that ONE transform of `n_points` points (all axes together) must meet, per item:
-    u (L + 2) and 4 u (L + 2) with L = log2(n_points); fp32 also keeps the reference's L1 threshold 1.1e-6 where it is the tighter.
-    The constants come from a radix-2 model with correctly rounded twiddles (tests/test_accuracy_model.py, which also shows that the
-    bound catches a twiddle table wrong in the 12th digit and a localised index error that the reference's thresholds let through)."""
+    u (L + 2) and 4 u (L + 2); fp32 also keeps the reference's L1 threshold 1.1e-6 where it is the tighter.  L = log2(n_points) for a
+    power of two; any other length must say which L its form earns (`levels`: any_size_levels).  The constants come from a radix-2
+    model with correctly rounded twiddles, and hold for the mixed-radix and Bluestein models of the extensions with L = ceil(log2 n)
+    and L = log2 of the padded length (tests/test_accuracy_model.py, which also shows that the bound catches a twiddle table wrong in
+    the 12th digit and a localised index error that the reference's thresholds let through)."""
     n_points = int(n_points)
-    assert n_points >= 1 and n_points & (n_points - 1) == 0, n_points
+    if levels is None:
+        assert n_points >= 1 and n_points & (n_points - 1) == 0, n_points
+        levels = n_points.bit_length() - 1
     u = unit_roundoff(dtype)
-    c = u * (n_points.bit_length() - 1 + 2)
+    c = u * (int(levels) + 2)
     l1 = c if u < 2.0 ** -30 else min(c, EPS_F)
     return l1, 4.0 * c
+
+
+def bluestein_padded_length(dtype, n):
+    """the m an axis of n points that Plan(..., any_size=True) runs by Bluestein's algorithm pads to: mifft_bluestein_padded's where the
+    one-launch kernel takes it, else the work array's 2^ceil(log2(2 n - 1))"""
+    from pyfft_amd import _native as N
+    prec = N.F64 if unit_roundoff(dtype) < 2.0 ** -30 else N.F32
+    mb = ctypes.c_int32(0)
+    if N.lib.mifft_bluestein_padded(prec, int(n), ctypes.byref(mb)) == 0:
+        return mb.value
+    return 1 << (2 * int(n) - 2).bit_length()
+
+
+def any_size_levels(shape, dtype):
+    """L of a Plan(shape, dtype, any_size=True) (the form selection of generic.GenericFFTPlan): ceil(log2) of the points of the axes
+    that run as powers of two, mixed-radix or long smooth transforms, plus ceil(log2 m) for every axis Bluestein pads to m.  The
+    power-of-two shapes keep L = log2(points)."""
+    from pyfft_amd import _native as N
+    shape = tuple(int(v) for v in (shape if isinstance(shape, (tuple, list)) else (shape,)))
+    prec = N.F64 if unit_roundoff(dtype) < 2.0 ** -30 else N.F32
+    split = numpy.dtype(dtype).kind == "f"
+    direct, levels = 1, 0
+    for n in shape:
+        if n & (n - 1) == 0 or N.lib.mifft_mixed_supported(prec, n) == 0:
+            direct *= n
+            continue
+        n1, n2 = ctypes.c_int32(0), ctypes.c_int32(0)
+        if all(v == 1 for v in shape[:-1]) and not split and \
+                N.lib.mifft_mixed_long_split(prec, n, ctypes.byref(n1), ctypes.byref(n2)) == 0:
+            direct *= n
+            continue
+        levels += bound_levels(bluestein_padded_length(dtype, n))
+    return levels + bound_levels(direct)
 
 
 def sampled_items(batch, n_points):
@@ -222,9 +266,9 @@ def item_error(got, ref):
     return float(diff.sum() / mag.sum()), float(diff.max() / numpy.sqrt(numpy.mean(mag * mag)))
 
 
-def check_accuracy(shape, dtype, batch, input_of, output_of, inverse=False, normalize=True, scale=1.0, what=""):
+def check_accuracy(shape, dtype, batch, input_of, output_of, inverse=False, normalize=True, scale=1.0, what="", levels=None):
     """Hold the sampled items (sampled_items) of a result to accuracy_bound.  input_of(j) / output_of(j): item j's exact input and the
-    path's output (complex, any shape of the item's size).  Returns {"l1", "max", "l1_ratio", "max_ratio", "item_l1", "item_max"}: the
+    path's output (complex, any shape of the item's size); `levels`: the L of accuracy_bound for a length that is no power of two.  Returns {"l1", "max", "l1_ratio", "max_ratio", "item_l1", "item_max"}: the
     WORST item's metrics, and the ratios metric / (u (L + 2)) that tests report."""
     from concurrent.futures import ThreadPoolExecutor
     shape = tuple(int(v) for v in (shape if isinstance(shape, (tuple, list)) else (shape,)))
@@ -240,8 +284,8 @@ def check_accuracy(shape, dtype, batch, input_of, output_of, inverse=False, norm
             errs = list(ex.map(one, items))
     else:
         errs = [one(j) for j in items]
-    l1_bound, max_bound = accuracy_bound(dtype, n)
-    unit = unit_roundoff(dtype) * (n.bit_length() - 1 + 2)
+    l1_bound, max_bound = accuracy_bound(dtype, n, levels)
+    unit = unit_roundoff(dtype) * ((n.bit_length() - 1 if levels is None else int(levels)) + 2)
     i1 = max(range(len(items)), key=lambda i: errs[i][0])
     im = max(range(len(items)), key=lambda i: errs[i][1])
     rep = {"l1": errs[i1][0], "max": errs[im][1], "l1_ratio": errs[i1][0] / unit, "max_ratio": errs[im][1] / unit,
@@ -294,3 +338,273 @@ class GuardedBuffer(object):
 
     def free(self):
         self.alloc.free()
+
+
+# ---- the steps of the per-instance contract, shared by tests/test_instances_gpu.py and tests/test_extension_instances_gpu.py --------
+OFFSETS = (16, 48, 208, 80, 144, 272)          # user-range offsets past the front guard: 16-byte aligned, none 64-byte aligned
+
+_blocks = {}
+_poison = {}
+
+
+def _block(cdt, count, seed):
+    """the first min(count, NOISE_PERIOD) elements of _test_data of `count` points: the data set repeats them (helpers._noise)"""
+    m = min(int(count), NOISE_PERIOD)
+    key = (numpy.dtype(cdt).name, m, seed)
+    if key not in _blocks:
+        if len(_blocks) > 8:
+            _blocks.clear()
+        _blocks[key] = _test_data((m,), cdt, 1, seed).reshape(-1)
+    return _blocks[key]
+
+
+class _Case(object):
+    """The guarded user buffers of one contract case: `batch` items of shape `shape` (tiles=(tile shape, counts (cz, cy, cx)): each
+    item a parent array, the accuracy checked per tile), in dtype `dtname`; levels = the L of accuracy_bound (None: a power of two)."""
+
+    def __init__(self, hip, N, case, index, tiles=None, levels=None):
+        shape, dtname, batch = case[:3]
+        self.hip, self.N = hip, N
+        self.shape, self.batch = tuple(shape), int(batch)
+        self.tiles, self.levels = tiles, levels
+        self.dtype = numpy.dtype(dtname)
+        self.split = self.dtype.kind == "f"
+        self.cdt = numpy.dtype(numpy.complex128 if self.dtype in (numpy.dtype(numpy.float64), numpy.dtype(numpy.complex128)) else numpy.complex64)
+        self.n = int(numpy.prod(self.shape))
+        self.count = self.n * self.batch
+        self.esize = self.cdt.itemsize // 2 if self.split else self.cdt.itemsize       # bytes per element of one plane
+        self.item_bytes = self.n * self.esize
+        self.plane_bytes = self.count * self.esize
+        planes = 2 if self.split else 1
+        o_in, o_out = OFFSETS[index % len(OFFSETS)], OFFSETS[(index + 1) % len(OFFSETS)]
+        self.ins, self.outs, self.x0, self.ref, self._word = [], [], [], [], None
+        try:
+            for _ in range(planes):
+                self.ins.append(GuardedBuffer(self.plane_bytes, o_in))
+                self.outs.append(GuardedBuffer(self.plane_bytes, o_out))
+                self.x0.append(hip.DeviceAllocation(self.plane_bytes))      # the input of step 1
+                self.ref.append(hip.DeviceAllocation(self.plane_bytes))     # the clean forward result the poisoned runs are compared with
+            w = ctypes.c_void_p()
+            N.check(N.lib.mifft_host_alloc(ctypes.byref(w), 64), "mifft_host_alloc")
+            self._word = w.value
+            self._count = ctypes.c_uint64.from_address(w.value)
+        except BaseException:
+            self.close()
+            raise
+
+    def close(self):
+        for b in self.ins + self.outs:
+            b.free()
+        for a in self.x0 + self.ref:
+            a.free()
+        if self._word is not None:
+            self.N.lib.mifft_host_free(self._word)
+            self._word = None
+
+    # -- device data
+    def _sync(self):
+        self.N.check(self.N.lib.mifft_device_sync(), "mifft_device_sync")
+
+    def _d2d(self, dst, src, nbytes):
+        self.N.check(self.N.lib.mifft_memcpy_d2d(dst, src, nbytes, None), "mifft_memcpy_d2d")
+
+    def _repeat(self, ptr, host, nbytes):
+        """ptr[0 .. nbytes) = `host` (bytes) repeated: one upload, then copies of what is already there"""
+        done = min(host.nbytes, nbytes)
+        self.N.check(self.N.lib.mifft_memcpy_h2d(ptr, host.ctypes.data, done, None), "mifft_memcpy_h2d")
+        while done < nbytes:
+            step = min(done - done % host.nbytes, nbytes - done)
+            self._d2d(ptr + done, ptr, step)
+            done += step
+
+    def fill(self, bufs, seed):
+        """the data set of _test_data(shape, dtype, batch, seed) into the planes `bufs`; returns the block it repeats"""
+        blk = _block(self.cdt, self.count, seed)
+        hosts = [numpy.ascontiguousarray(blk.real), numpy.ascontiguousarray(blk.imag)] if self.split else [blk]
+        for b, h in zip(bufs, hosts):
+            self._repeat(b.ptr, h.view(numpy.uint8), self.plane_bytes)
+        self._sync()
+        return blk
+
+    def item_input(self, blk, j):
+        return blk[(j * self.n + numpy.arange(self.n, dtype=numpy.int64)) % blk.size]
+
+    def item_planes(self, ptrs, j):
+        """item j of the planes at `ptrs`, as host arrays of the plane dtype"""
+        parts = []
+        for p in ptrs:
+            h = numpy.empty(self.n, self.cdt.type(0).real.dtype if self.split else self.cdt)
+            self.N.check(self.N.lib.mifft_memcpy_d2h(h.ctypes.data, p + j * self.item_bytes, self.item_bytes, None), "mifft_memcpy_d2h")
+            parts.append(h)
+        return parts
+
+    def item_output(self, bufs, j):
+        parts = self.item_planes([b.ptr for b in bufs], j)
+        return parts[0].astype(self.cdt) + 1j * parts[1] if self.split else parts[0]
+
+    def poison(self, ptr, j, value):
+        """item j of the plane at `ptr` all `value` (not synchronised)"""
+        fdt = numpy.float64 if self.cdt == numpy.complex128 else numpy.float32
+        key = (value, fdt)
+        if key not in _poison:
+            _poison[key] = numpy.full(1 << 17, value, fdt).view(numpy.uint8)
+        host = _poison[key][:min(self.item_bytes, _poison[key].nbytes)]
+        self._repeat(ptr + j * self.item_bytes, host, self.item_bytes)
+
+    def mismatches(self, a, b, nbytes):
+        """how much of device ranges a[0 .. nbytes) and b[0 .. nbytes) differs: 16-byte words on the device, bytes on the host (small or odd
+        ranges); 0 when they are bit-identical"""
+        if nbytes <= 0:
+            return 0
+        if nbytes % 16 or (a | b) % 16 or nbytes < 4096:
+            ha, hb = numpy.empty(nbytes, numpy.uint8), numpy.empty(nbytes, numpy.uint8)
+            self.N.check(self.N.lib.mifft_memcpy_d2h(ha.ctypes.data, a, nbytes, None), "mifft_memcpy_d2h")
+            self.N.check(self.N.lib.mifft_memcpy_d2h(hb.ctypes.data, b, nbytes, None), "mifft_memcpy_d2h")
+            return int(numpy.count_nonzero(ha != hb))
+        self._count.value = 0
+        self.N.check(self.N.lib.mifft_aux_count_mismatch(a, b, nbytes, self._word, None), "mifft_aux_count_mismatch")
+        self._sync()
+        return int(self._count.value)
+
+    def guards(self, bufs, what):
+        for i, b in enumerate(bufs):
+            b.check_guards("%s, plane %d" % (what, i))
+
+    # -- the accuracy of a result: per item, or per tile of every parent array
+    def tile_of(self, item, t):
+        """tile t (in the order [cz][cy][cx]) of one parent array `item` (flat)"""
+        tile, counts = self.tiles
+        full = tuple(a * b for a, b in zip(tile, counts[-len(tile):]))
+        idx = numpy.unravel_index(t, counts[-len(tile):])
+        sl = tuple(slice(i * a, (i + 1) * a) for i, a in zip(idx, tile))
+        return numpy.asarray(item).reshape(full)[sl]
+
+    def accuracy(self, bufs, blk, inverse=False, normalize=True, scale=1.0, what=""):
+        if self.tiles is None:
+            return check_accuracy(self.shape, self.dtype, self.batch, lambda j: self.item_input(blk, j), lambda j: self.item_output(bufs, j),
+                                  inverse=inverse, normalize=normalize, scale=scale, what=what, levels=self.levels)
+        tile, counts = self.tiles
+        nt = int(numpy.prod(counts))
+        last = {}
+
+        def out_item(p):
+            if p not in last:
+                last.clear()
+                last[p] = self.item_output(bufs, p)
+            return last[p]
+        return check_accuracy(tile, self.dtype, self.batch * nt, lambda j: self.tile_of(self.item_input(blk, j // nt), j % nt),
+                              lambda j: self.tile_of(out_item(j // nt), j % nt), inverse=inverse, normalize=normalize, scale=scale,
+                              what=what, levels=self.levels)
+
+
+def _poison_layouts(batch):
+    """{item: (plane, value)} of the poisoned runs: the middle item NaN and the last (ragged tile) +Inf; then every even item, NaN and +Inf
+    in turn, so that every odd item lies between two poisoned ones (with batch 3 the first layout checks item 0, the second item 1)"""
+    yield {batch // 2: (0, numpy.nan), batch - 1: (-1, numpy.inf)}
+    yield {j: ((0, numpy.nan) if j % 4 == 0 else (-1, numpy.inf)) for j in range(0, batch, 2)}
+
+
+def run_contract(plan, c, oop_differs, record_property):
+    """Steps 1-4 of the per-instance contract (tests/test_instances_gpu.py) on the buffers of `c` (a _Case) through `plan`.  Leaves the
+    clean forward result in c.ref; returns the reports [(step name, check_accuracy report)], which it also records."""
+    N = c.N
+    batch = c.batch
+    ins, outs = c.ins, c.outs
+
+    def run(src, dst=None, inverse=False):
+        args = [b.ptr for b in src] + ([b.ptr for b in dst] if dst is not None else [])
+        plan.execute(*args, batch=batch, inverse=inverse)
+
+    def clear_outputs():
+        for b in outs:
+            N.check(N.lib.mifft_memset(b.ptr, 0xFF, b.nbytes, None), "mifft_memset")      # (all-ones: a NaN in both precisions)
+
+    def inverse(inplace, blk3):
+        """3. inverse (normalize on) on fresh data"""
+        what = "in-place inverse" if inplace else "out-of-place inverse"
+        c.fill(outs if inplace else ins, 202)
+        if inplace:
+            run(outs, inverse=True)
+        else:
+            clear_outputs()
+            run(ins, outs, inverse=True)
+        c._sync()
+        if not inplace:
+            c.guards(ins, what + ", input")
+        c.guards(outs, what + ", output")
+        return c.accuracy(outs, blk3, inverse=True, what=what)
+
+    def isolation(inplace):
+        """4. poisoned items: every other item bit-identical to the clean forward result in c.ref"""
+        what = "in-place" if inplace else "out-of-place"
+        src = outs if inplace else ins
+        ib = c.item_bytes
+        for layout in _poison_layouts(batch):
+            for b, x in zip(src, c.x0):
+                c._d2d(b.ptr, x.ptr, c.plane_bytes)
+            for j, (plane, value) in layout.items():
+                c.poison(src[plane].ptr, j, value)
+            if inplace:
+                run(outs)
+            else:
+                clear_outputs()
+                run(ins, outs)
+            c._sync()
+            if not inplace:
+                c.guards(ins, "poisoned %s forward, input" % what)
+            c.guards(outs, "poisoned %s forward, output" % what)
+            for j in layout:                                 # (the poisoned items' own results are not compared)
+                for b, r in zip(outs, c.ref):
+                    c._d2d(b.ptr + j * ib, r.ptr + j * ib, ib)
+            c._sync()
+            for b, r in zip(outs, c.ref):
+                if c.mismatches(b.ptr, r.ptr, c.plane_bytes):
+                    changed = [j for j in range(min(batch, 4096)) if c.mismatches(b.ptr + j * ib, r.ptr + j * ib, ib)]
+                    raise AssertionError("%s forward: items %r changed when items %r were poisoned" % (what, changed[:20], sorted(layout)[:20]))
+
+    # 1. out of place, forward
+    blk = c.fill(ins, 101)
+    for b, x in zip(ins, c.x0):
+        c._d2d(x.ptr, b.ptr, c.plane_bytes)
+    clear_outputs()
+    run(ins, outs)
+    c._sync()
+    for b, x in zip(ins, c.x0):
+        assert c.mismatches(b.ptr, x.ptr, c.plane_bytes) == 0, "an out-of-place execute touched its input"
+    c.guards(ins, "out-of-place forward, input")
+    c.guards(outs, "out-of-place forward, output")
+    fw = c.accuracy(outs, blk, what="out of place")
+    for b, r in zip(outs, c.ref):
+        c._d2d(r.ptr, b.ptr, c.plane_bytes)
+
+    # 2. in place, forward
+    for b, x in zip(outs, c.x0):
+        c._d2d(b.ptr, x.ptr, c.plane_bytes)
+    run(outs)
+    c._sync()
+    c.guards(outs, "in-place forward")
+    if oop_differs:
+        c.accuracy(outs, blk, what="in place")
+    else:
+        for b, r in zip(outs, c.ref):
+            assert c.mismatches(b.ptr, r.ptr, c.plane_bytes) == 0, "in place differs from out of place"
+
+    # 3. + 4. out of place; and in place where that runs another instance (c.ref then holds the in-place result)
+    blk3 = _block(c.cdt, c.count, 202)
+    inv = inverse(False, blk3)
+    isolation(False)
+    reps = [("forward", fw), ("inverse", inv)]
+    if oop_differs:
+        for b, x in zip(outs, c.x0):
+            c._d2d(b.ptr, x.ptr, c.plane_bytes)
+        run(outs)
+        c._sync()
+        for b, r in zip(outs, c.ref):
+            c._d2d(r.ptr, b.ptr, c.plane_bytes)
+        reps.append(("inplace_inverse", inverse(True, blk3)))
+        isolation(True)
+
+    for name, rep in reps:
+        record_property(name + "_l1_ratio", "%.4g" % rep["l1_ratio"])
+        record_property(name + "_max_ratio", "%.4g" % rep["max_ratio"])
+    return reps

@@ -26,7 +26,7 @@ from helpers import FakeContext
 
 GPU_MODULES = ["test_errors_gpu", "test_full_size_gpu", "test_functionality_gpu", "test_random_sweep_gpu", "test_rows_gpu",
                "test_strided_gpu", "test_persistent_gpu", "test_pairs_gpu", "test_nd_gpu", "test_generic_gpu", "test_interop_gpu",
-               "test_instances_gpu"]
+               "test_instances_gpu", "test_extension_instances_gpu"]
 
 C64, C128, F32, F64 = numpy.complex64, numpy.complex128, numpy.float32, numpy.float64
 ALL_DTYPES = [C64, F32, C128, F64]
@@ -462,7 +462,7 @@ REGISTRY = {
         "test_dense_split_planes_on_the_tiled_fixed_kernels": lambda p: [_c(p["shape"], p["dtype"], p["batch"])],
         "test_dense_split_planes_16_byte_accesses": lambda p: [_c(p["shape"], p["dtype"], 1)],
     },
-    "test_generic_gpu": None,            # opt-in extensions (any_size / parent_shape): their inner power-of-two plans are ordinary plans
+    "test_generic_gpu": None,            # opt-in extensions (any_size / parent_shape): their kernels are extension keys (extension_universe)
     "test_interop_gpu": {
         "test_reference_quick_start_literally": lambda p: [_c((1 << 22,), C64, 1)],
         "test_default_plan_orders_against_torch_producer": lambda p: [_c((1 << 20,), C64, 64)],
@@ -485,6 +485,9 @@ REGISTRY = {
     },
     "test_instances_gpu": {
         "test_instance": lambda p: [_c(p["case"][0], numpy.dtype(p["case"][1]).type, p["case"][2])],
+    },
+    "test_extension_instances_gpu": {
+        "test_extension_instance": None,     # (extension keys: extension_covered_keys)
     },
 }
 
@@ -530,4 +533,255 @@ def covered_keys(cases=None):
         for k in keys_of(shape, dtype, batch, mode):
             if k is not None:
                 out.setdefault(k, (modname, f))
+    return out
+
+
+# ---- the opt-in extensions (pyfft_amd/generic.py: Plan(..., any_size=True), Plan(tile, parent_shape=...)) ----------------------------
+# Their kernels (csrc/fft_mixed.hip, fft_mixed_nd.hip, fft_nd2t*.hip) are instances no power-of-two plan selects.  The form a plan takes
+# is GenericFFTPlan's own selection, run here on the model of the full part (a plan on FakeContext: tables are uploaded nowhere); the
+# launch geometry comes from the library's host queries (mifft_mixed_radices, mifft_mixed_long_split, mifft_bluestein_padded,
+# mifft_mixed_nd_supported, mifft_nd_tiled_supported).
+#   mixed_row   (prec, n)                       every smooth length of one tile that is no power of two: every radix list of the rows
+#   mixed_stage (instance, prec, R, position)   the stage loops of the lines kernel (MODE 1), the long transform's first pass (MODE 2),
+#                                               the N-D kernel, both Bluestein kernels: every radix first / middle / last in the list
+#   blue1       (prec, tile | big)              the one-launch Bluestein kernel on a 1-D length
+#   blue_work   (prec, layout, 1d | nd, pow2 | one_launch)   Bluestein axes on the work array
+#   tiled       (prec, layout, tile shape)      one launch straight on the parent array
+#   long        (prec, largest | beyond)        the largest N mifft_mixed_long_split takes; the next smooth N, which takes Bluestein
+#   split       (prec, form)                    split planes through the work array (gather / scatter)
+_ext_plans = {}
+
+
+def ext_plan(shape, dtype, parent=None):
+    """a GenericFFTPlan on FakeContext, cached: its tables go nowhere, so they are not evaluated either (zeros of the right length)"""
+    from pyfft_amd import generic
+    key = (tuple(shape), numpy.dtype(dtype).name, parent)
+    if key not in _ext_plans:
+        kw = {"parent_shape": parent} if parent is not None else {"any_size": True}
+        saved = generic._unit_roots, generic._chirp, generic._bluestein_spectrum
+        generic._unit_roots = lambda count, step, period: numpy.zeros(count, numpy.complex128)
+        generic._chirp = lambda n, *a: numpy.zeros(n, numpy.complex128)
+        generic._bluestein_spectrum = lambda n, m: numpy.zeros(m, numpy.complex128)
+        try:
+            _ext_plans[key] = generic.GenericFFTPlan(FakeContext(full_machine()), tuple(shape), dtype=dtype, **kw)
+        finally:
+            generic._unit_roots, generic._chirp, generic._bluestein_spectrum = saved
+    return _ext_plans[key]
+
+
+def _prec_name(dtype):
+    return "f64" if _is_double(dtype) else "f32"
+
+
+def mixed_radices(n):
+    import ctypes
+    from pyfft_amd import _native as N
+    r = (ctypes.c_int32 * N.MIFFT_MIXED_MAX_STAGES)()
+    k = N.lib.mifft_mixed_radices(N.F32, int(n), r)
+    assert k > 0, n
+    return list(r[:k])
+
+
+def _stage_keys(instance, prec, lengths):
+    """(mixed_stage, instance, prec, R, position) of a launch whose stage list is the radix lists of `lengths`, one after the other"""
+    rad = list(itertools.chain.from_iterable(mixed_radices(n) for n in lengths if n > 1))
+    out = set()
+    for i, R in enumerate(rad):
+        if i == 0:
+            out.add(("mixed_stage", instance, prec, R, "first"))
+        if i == len(rad) - 1:
+            out.add(("mixed_stage", instance, prec, R, "last"))
+        if 0 < i < len(rad) - 1:
+            out.add(("mixed_stage", instance, prec, R, "middle"))
+    return out
+
+
+def form_of(plan):
+    """the attribute of the form a GenericFFTPlan takes"""
+    for f in ("_tiled", "_direct_nd1", "_direct_nd_planes", "_direct_long", "_direct_blue", "_direct_mixed"):
+        if getattr(plan, f):
+            return f
+    if plan._direct_nd is not None:
+        return "_direct_nd"
+    return "_uses_work"
+
+
+def extension_keys(shape, dtype, parent=None):
+    """the extension keys one plan exercises (any batch: every form runs the same kernels at every batch)"""
+    from pyfft_amd.generic import _is_pow2
+    plan = ext_plan(shape, dtype, parent)
+    prec = _prec_name(dtype)
+    lay = "split" if _split(dtype) else "interleaved"
+    x, y, z = plan._xyz
+    form = form_of(plan)
+    keys = set()
+    if form == "_tiled":
+        keys.add(("tiled", prec, lay, (x, y, z)))
+    elif form == "_direct_mixed":
+        keys.add(("mixed_row", prec, x))
+    elif form == "_direct_nd1":
+        keys |= _stage_keys("nd", prec, (x, y, z))
+    elif form == "_direct_nd_planes":
+        keys |= _stage_keys("nd", prec, (x, y)) | _stage_keys("lines", prec, (z,))
+    elif form == "_direct_nd":
+        for a, n in enumerate((x, y, z)):
+            if n > 1 and a > 0 and (x, y, z)[:a] != (1,) * a:
+                keys |= _stage_keys("lines", prec, (n,))
+    elif form == "_direct_long":
+        n1, n2 = plan._direct_long[:2]
+        keys |= _stage_keys("long_first", prec, (n1,)) | _stage_keys("lines", prec, (n2,))
+        keys.add(("long", prec))
+        if x == long_limits(dtype)[0]:
+            keys.add(("long", prec, "largest"))
+    elif form == "_direct_blue":
+        m = plan._axes[0].blue[0]
+        big = m > (2048 if prec == "f64" else 4096)
+        keys.add(("blue1", prec, "big" if big else "tile"))
+        keys |= _stage_keys("blue_big" if big else "blue", prec, (m,))
+    else:
+        dims = "1d" if (y, z) == (1, 1) else "nd"
+        if dims == "1d" and not _split(dtype) and x == long_limits(dtype)[1]:
+            keys.add(("long", prec, "beyond"))
+        for ax in plan._axes:
+            if ax.blue is not None:
+                keys.add(("blue_work", prec, lay, dims, "one_launch"))
+            elif not ax.pow2 and ax.mixed_tw is None:
+                keys.add(("blue_work", prec, lay, dims, "pow2"))
+        if lay == "split":
+            keys.add(("split", prec, "tiles" if parent is not None else ("pow2" if all(_is_pow2(v) for v in (x, y, z)) else "any_size")))
+    return keys
+
+
+def _smooth_upto(limit):
+    out = []
+    for n in range(2, limit + 1):
+        m = n
+        for c in (2, 3, 5, 7):
+            while m % c == 0:
+                m //= c
+        if m == 1:
+            out.append(n)
+    return out
+
+
+def long_limits(dtype):
+    """(the largest N mifft_mixed_long_split takes, the smallest smooth N beyond it) for the precision of `dtype`"""
+    prec = _prec_name(dtype)
+    if prec not in _long_limits:
+        _long_limits[prec] = _long_limits_of(dtype)
+    return _long_limits[prec]
+
+
+_long_limits = {}
+
+
+def _long_limits_of(dtype):
+    import ctypes
+    from pyfft_amd import _native as N
+    prec = N.F64 if _is_double(dtype) else N.F32
+    a, b = ctypes.c_int32(0), ctypes.c_int32(0)
+    ok = [n for n in _smooth_upto(1 << 20) if n > 4096 and N.lib.mifft_mixed_long_split(prec, n, ctypes.byref(a), ctypes.byref(b)) == 0]
+    top = max(ok)
+    beyond = min(n for n in _smooth_upto(1 << 21) if n > top)
+    return top, beyond
+
+
+def tiled_tile_shapes(dtype):
+    """numpy tile shapes (2-D and 3-D, power-of-two axes up to 256) with a one-launch tiled kernel (mifft_nd_tiled_supported)"""
+    from pyfft_amd import _native as N
+    prec = N.F64 if _is_double(dtype) else N.F32
+    pows = [1 << k for k in range(0, 9)]
+    out = []
+    for z in pows[:7]:
+        for y in pows:
+            for x in pows:
+                if (x > 1) + (y > 1) + (z > 1) < 2 or x * y * z > (1 << 16):
+                    continue
+                if N.lib.mifft_nd_shape_supported(prec, x, y, z, N.VARIANT_INTERLEAVED_ONLY) == 0 and N.lib.mifft_nd_tiled_supported(prec, x, y, z) == 0:
+                    out.append((y, x) if z == 1 else (z, y, x))
+    return out
+
+
+def _ext_candidates():
+    """(shape, dtype, parent) of the candidate plans: every 1-D length up to 5000 (the one-launch Bluestein limit), the long limits,
+    2-D / 3-D shapes of smooth and prime axes, the tiled tile shapes, in the four dtypes"""
+    small = _smooth_upto(64)
+    for dtype in ALL_DTYPES:
+        for n in (range(3, 5001) if not _split(dtype) else (12, 17, 1009, 4099, 5000)):
+            if n & (n - 1):
+                yield (n,), dtype, None
+        top, beyond = long_limits(dtype)
+        yield (top,), dtype, None
+        yield (beyond,), dtype, None
+        for yv in small + [100, 128, 210, 256, 512, 1000]:
+            for xv in (3, 5, 7, 12, 15, 16, 60, 64, 100, 210, 1000):
+                if (xv & (xv - 1)) or (yv & (yv - 1)):
+                    yield (yv, xv), dtype, None
+        for sh in ((12, 10, 14), (60, 60, 60), (5, 6, 7), (9, 8, 15), (6, 64, 64), (3, 128, 128)):
+            yield sh, dtype, None
+        for sh in ((17, 4), (4, 17), (5000, 4), (4099, 4), (3, 17, 4), (4, 1009)):
+            yield sh, dtype, None
+        for t in tiled_tile_shapes(dtype):
+            yield t, dtype, tuple(v * f for v, f in zip(t, (2, 3, 2)))
+        yield (16, 4), dtype, (64, 64)
+
+
+_ext_table = []
+
+
+def _ext_candidate_keys():
+    """[(order, shape, dtype, parent, bytes per item, keys)] of every candidate (computed once)"""
+    if not _ext_table:
+        for order, (shape, dtype, parent) in enumerate(_ext_candidates()):
+            size = _prod(parent if parent is not None else shape) * (16 if _is_double(dtype) else 8)
+            _ext_table.append((order, shape, dtype, parent, size, extension_keys(shape, dtype, parent)))
+    return _ext_table
+
+
+def extension_universe():
+    """{key: the first candidate (shape, dtype name, parent) that selects it}"""
+    out = {}
+    for order, shape, dtype, parent, size, keys in _ext_candidate_keys():
+        for k in keys:
+            out.setdefault(k, (shape, numpy.dtype(dtype).name, parent))
+    return out
+
+
+def _ragged_batch(shape, dtype, parent):
+    """at least 3 items, and a last work-group that is partly filled: rows (items times the lines of an axis) no multiple of the
+    work-group's count where a work-group holds several"""
+    n = _prod(shape)
+    full = 2048 if _is_double(dtype) else 4096
+    if parent is not None or len(shape) > 1 or n > full // 2:
+        return 3
+    W = (full // 2) // n
+    return 2 * W + 1 if W > 1 else 3
+
+
+def extension_audit_cases():
+    """[(shape, dtype name, batch, parent, form, keys)]: for every key of extension_universe(), the smallest candidate that selects it
+    (bytes per item, then the candidate order); a candidate that is the smallest for several keys appears once"""
+    best = {}
+    for order, shape, dtype, parent, size, keys in _ext_candidate_keys():
+        for k in keys:
+            if k not in best or (size, order) < best[k][:2]:
+                best[k] = (size, order, shape, dtype, parent)
+    cases = {}
+    for k, (_, order, shape, dtype, parent) in best.items():
+        cases.setdefault((order, shape, dtype, parent), []).append(k)
+    out = []
+    for (order, shape, dtype, parent), ks in sorted(cases.items(), key=lambda kv: kv[0][0]):
+        form = form_of(ext_plan(shape, dtype, parent))
+        out.append((shape, numpy.dtype(dtype).name, _ragged_batch(shape, dtype, parent), parent, form, tuple(sorted(ks, key=str))))
+    return out
+
+
+def extension_covered_keys():
+    """{key: case} over the cases of tests/test_extension_instances_gpu.py, read off its parametrize mark"""
+    mod = importlib.import_module("test_extension_instances_gpu")
+    out = {}
+    for p in params_of(mod.test_extension_instance):
+        shape, dtname, batch, parent, form, keys = p["case"]
+        for k in extension_keys(shape, numpy.dtype(dtname), parent):
+            out.setdefault(k, p["case"])
     return out

@@ -60,3 +60,40 @@ def test_registry_names_every_gpu_test_function():
     assert len(cases) > 1800
     mods = set(m for m, _, _ in cases)
     assert {"test_errors_gpu", "test_persistent_gpu", "test_pairs_gpu", "test_nd_gpu", "test_strided_gpu", "test_interop_gpu"} <= mods
+
+
+def test_every_extension_kernel_instance_has_a_contract_case():
+    """The opt-in extensions' kernels (kernel_coverage.extension_universe(): mixed-radix rows, lines, long transforms, the N-D and both
+    Bluestein kernels, Bluestein axes on the work array, the tiled kernels, split planes) each run in tests/test_extension_instances_gpu.py."""
+    uni = KC.extension_universe()
+    kinds = {}
+    for k in uni:
+        kinds[k[0]] = kinds.get(k[0], 0) + 1
+    assert kinds["mixed_row"] == 235 + 178
+    assert kinds["mixed_stage"] >= 200 and kinds["tiled"] >= 2 * 2 * 13 and kinds["blue1"] == 4 and kinds["blue_work"] >= 10
+    assert kinds["long"] == 6 and kinds["split"] >= 4
+    stages = set(k[1] for k in uni if k[0] == "mixed_stage")
+    assert stages == {"lines", "long_first", "nd", "blue", "blue_big"}, stages
+    for prec in ("f32", "f64"):
+        assert ("blue_work", prec, "interleaved", "nd", "one_launch") in uni and ("long", prec, "beyond") in uni
+        for inst in ("lines", "nd", "blue"):
+            for R in (3, 5, 7):
+                assert ("mixed_stage", inst, prec, R, "first") in uni, (inst, prec, R)
+    cov = KC.extension_covered_keys()
+    missing = sorted(set(uni) - set(cov), key=str)
+    assert not missing, "extension kernel instances without a contract case: %r" % (missing[:40],)
+
+
+def test_extension_cases_take_their_forms_and_ragged_batches():
+    top32, beyond32 = KC.long_limits(numpy.complex64)
+    top64, beyond64 = KC.long_limits(numpy.complex128)
+    assert top32 < beyond32 < (1 << 18) + (1 << 16) and top64 < beyond64
+    cases = KC.extension_audit_cases()
+    forms = set(c[4] for c in cases)
+    assert forms >= {"_direct_mixed", "_direct_nd", "_direct_nd1", "_direct_nd_planes", "_direct_long", "_direct_blue", "_tiled", "_uses_work"}
+    for shape, dtname, batch, parent, form, keys in cases:
+        assert batch >= 3
+        if form == "_direct_mixed" and batch > 3:
+            assert batch % ((4096 if dtname == "complex64" else 2048) // 2 // shape[0]) != 0
+    for dt in ("float32", "float64"):
+        assert any(c[1] == dt and c[3] is None and c[4] == "_uses_work" for c in cases), dt
