@@ -506,6 +506,21 @@ int mifft_real_row_supported(int32_t precision, int32_t n);
 int mifft_launch_real_row(int32_t precision, int32_t n, int32_t inverse, int64_t rows, const void *in, void *out, const void *tw_half,
                           const void *tw_sep, double scale, mifft_stream_t stream);
 
+/* Convolution rows (docs/extensions.md "Convolution plans"): y = scale * IFFT(FFT(x) * S) per row in ONE launch, S = H or, with
+ * correlate = 1, conj(H); IFFT unnormalised (the caller folds 1 / n into scale).  real = 0: rows of n interleaved complex numbers, H n
+ * complex numbers; real = 1: rows of n reals, H the n / 2 + 1 point half spectrum (numpy's rfft layout; H[0] and H[n / 2] products
+ * through their real parts, as numpy's irfft).  rows dense; in == out (in place) or disjoint.  spectrum_pitch: complex numbers between
+ * the spectra of consecutive rows, 0 = one spectrum shared by every row; the spectrum must not overlap in or out and is never written.
+ * tw = device table w(L)^k (L = n complex, n / 2 real), tw_sep = w(n)^k (n / 2 + 1 entries; real only), the precision's complex type.
+ *   mifft_conv_row_supported   0 if a kernel exists for (precision, real, n), else MIFFT_E_UNSUPPORTED
+ *   mifft_aux_mul_spectrum     data[i][j] *= scale * S[i * spectrum_pitch + j], items x points interleaved complex numbers (the composed
+ *                              form's spectrum product) */
+int mifft_conv_row_supported(int32_t precision, int32_t real, int32_t n);
+int mifft_launch_conv_row(int32_t precision, int32_t real, int32_t n, int64_t rows, const void *in, void *out, const void *spectrum,
+                          int64_t spectrum_pitch, int32_t correlate, const void *tw, const void *tw_sep, double scale, mifft_stream_t stream);
+int mifft_aux_mul_spectrum(int32_t precision, void *data, const void *spectrum, int64_t items, int64_t points, int64_t spectrum_pitch,
+                           int32_t correlate, double scale, mifft_stream_t stream);
+
 /* Half-precision (complex32) transforms (docs/extensions.md "Half-precision transforms"): interleaved fp16 data, one fp16 real and one
  * fp16 imaginary part per point (4 bytes).  Loads widen to fp32 exactly, every stage runs in fp32 on the fp32 twiddle tables, and the
  * result (times scale, in fp32) is rounded to fp16 once, to nearest even, at the store: beyond +-65504 it is +-inf, NaN stays NaN.

@@ -230,6 +230,9 @@ PROTOTYPES = {
     "mifft_launch_real_post": (ctypes.c_int, [ctypes.POINTER(MifftRealPost), _vp]),
     "mifft_real_row_supported": (ctypes.c_int, [_i32, _i32]),
     "mifft_launch_real_row": (ctypes.c_int, [_i32, _i32, _i32, ctypes.c_int64, _vp, _vp, _vp, _vp, ctypes.c_double, _vp]),
+    "mifft_conv_row_supported": (ctypes.c_int, [_i32, _i32, _i32]),
+    "mifft_launch_conv_row": (ctypes.c_int, [_i32, _i32, _i32, ctypes.c_int64, _vp, _vp, _vp, ctypes.c_int64, _i32, _vp, _vp, ctypes.c_double, _vp]),
+    "mifft_aux_mul_spectrum": (ctypes.c_int, [_i32, _vp, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _i32, ctypes.c_double, _vp]),
     "mifft_half_supported": (ctypes.c_int, [_i32, _i32, _i32]),
     "mifft_half_kernel": (ctypes.c_int, [_i32, _i32, _i32, _i32]),
     "mifft_launch_half": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _vp]),

@@ -84,6 +84,26 @@ template <typename T> __global__ void __launch_bounds__(256) aux_mul_rows_kernel
         a[id] = mifft::cmul<T>(a[id], b[id % n]);
 }
 
+// Convolution plans' composed form (pyfft_amd/conv.py): data[i][j] *= scale * S[i * pitch + j], S = conj(spectrum) when correlating.
+// blockIdx.x covers the item's points (V consecutive per thread: 16-byte accesses), blockIdx.y strides over the items, so no index is
+// divided; a shared spectrum (pitch 0) is read from the L2 by every item.
+template <typename T, int V>
+__global__ void __launch_bounds__(256) aux_mul_spectrum_kernel(mifft::cplx<T>* data, const mifft::cplx<T>* spec, long long items, long long points,
+                                                               long long pitch, int correlate, double scale) {
+    const long long j = ((long long)blockIdx.x * 256 + threadIdx.x) * V;
+    if (j >= points) return;
+    const T sc = (T)scale, sy = correlate ? -sc : sc;
+    mifft::cplx<T> h[V];
+    for (long long i = blockIdx.y; i < items; i += gridDim.y) {
+        const mifft::cplx<T>* si = spec + i * pitch + j;
+        mifft::cplx<T>* di = data + i * points + j;
+#pragma unroll
+        for (int v = 0; v < V; ++v) h[v] = mifft::cplx<T>{si[v].x * sc, si[v].y * sy};
+#pragma unroll
+        for (int v = 0; v < V; ++v) di[v] = mifft::cmul<T>(di[v], h[v]);
+    }
+}
+
 unsigned grid_for(long long total) {
     long long g = (total + 255) / 256;
     if (g > 256 * 32) g = 256 * 32;
@@ -131,6 +151,29 @@ extern "C" int mifft_aux_mul_rows_launch(int f64, void* a, const void* b, long l
     if (total <= 0) return 0;
     if (f64) hipLaunchKernelGGL(aux_mul_rows_kernel<double>, dim3(grid_for(total)), dim3(256), 0, s, (mifft::cplx<double>*)a, (const mifft::cplx<double>*)b, total, n);
     else hipLaunchKernelGGL(aux_mul_rows_kernel<float>, dim3(grid_for(total)), dim3(256), 0, s, (mifft::cplx<float>*)a, (const mifft::cplx<float>*)b, total, n);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mifft_aux_mul_spectrum_launch(int f64, void* data, const void* spectrum, long long items, long long points, long long pitch,
+                                             int correlate, double scale, hipStream_t s) {
+    if (items <= 0) return 0;
+    // two fp32 points per thread where every item's run stays 16-byte aligned
+    const bool pair = !f64 && (points & 1) == 0 && (pitch & 1) == 0 && (((uintptr_t)data | (uintptr_t)spectrum) & 15) == 0;
+    const long long per = pair ? 512 : 256;
+    const long long gx = (points + per - 1) / per;
+    if (gx > 2147483647ll) return -1;
+    const long long want_y = (1ll << 16) / (gx < 1 ? 1 : gx);
+    const unsigned gy = (unsigned)(items < want_y ? items : (want_y < 1 ? 1 : (want_y > 65535 ? 65535 : want_y)));
+    const dim3 grid((unsigned)gx, gy);
+    if (f64)
+        hipLaunchKernelGGL((aux_mul_spectrum_kernel<double, 1>), grid, dim3(256), 0, s, (mifft::cplx<double>*)data,
+                           (const mifft::cplx<double>*)spectrum, items, points, pitch, correlate, scale);
+    else if (pair)
+        hipLaunchKernelGGL((aux_mul_spectrum_kernel<float, 2>), grid, dim3(256), 0, s, (mifft::cplx<float>*)data,
+                           (const mifft::cplx<float>*)spectrum, items, points, pitch, correlate, scale);
+    else
+        hipLaunchKernelGGL((aux_mul_spectrum_kernel<float, 1>), grid, dim3(256), 0, s, (mifft::cplx<float>*)data,
+                           (const mifft::cplx<float>*)spectrum, items, points, pitch, correlate, scale);
     return (int)hipGetLastError();
 }
 

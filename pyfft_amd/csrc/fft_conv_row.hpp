@@ -1,0 +1,266 @@
+// One-launch convolution rows (Plan(n, convolve=True), docs/extensions.md "Convolution plans"): y = scale * IFFT(FFT(x) * S) per row,
+// S = H or conj(H), in ONE work-group, so that a row crosses HBM once: n s bytes in, n s bytes out, plus the spectrum (from L2 / MALL
+// when it is shared by every row).
+//   complex  the fft_row2.hpp stages of the forward L = n point transform; instead of the last stage's stores ConvEpi multiplies every
+//            point by S[idx] in the thread that holds it (register i = b*R + k is point b*TPR + k*LR + tid), then the inverse runs as a
+//            forward transform of the conjugate, IFFT(Y) = conj(FFT(conj Y)) / n, through the preloaded stage entry with
+//            TileArgs::inverse set: its first stage negates the imaginary parts in registers, its stores negate them again and apply
+//            the scale (1/n folded in by the host), so one twiddle table serves both directions.
+//            The inverse takes the REVERSED radix list: its first radix is the forward's last, so the forward's last-stage register
+//            layout is the inverse's first-stage load layout for every list, and no LDS exchange joins the two transforms.
+//   real     n real points as L = n / 2 packed complex points (csrc/fft_real.hip states the identities).  The forward packed stages run;
+//            one mirror exchange through the row's LDS slab (as RealSepEpi) gives the thread that holds Z[k] also Z[L - k]; from that
+//            pair it derives X[k] and X[L - k], multiplies them by S[k] and S[L - k] and packs Z'[k] from the two products -- exactly
+//            the pair the packing identity needs, so no second exchange.  Index 0 takes X[0] and X[L] through their real parts (the
+//            edge rule of real_row_inv_kernel, numpy's irfft).  The inverse L-point stages store the n reals.
+// Rows of L <= 32 (complex or packed points): one thread per row, both transforms in registers (Dft<L>), as real_row_small_kernel.
+// Work-group shapes and forward radix lists are those of the real rows of L packed points (fft_real_row_f32.hip / _f64.hip): the complex
+// row instances of L >= 256 points, and the register-edged form for L = 64, 128 too (the complex ROW dispatch runs the LDS-staged tile
+// kernel there, which has no register epilogue).
+#pragma once
+#include <type_traits>
+#include "fft_real_row.hpp"
+
+namespace mifft {
+
+struct ConvRowArgs {
+    const void* in;          // rows of L complex numbers (complex) or n = 2L reals (real), dense
+    void* out;               // the same layout; may equal `in`
+    const void* spec;        // interleaved complex: L (complex) or L + 1 (real) points per spectrum
+    const void* tw;          // w(L)^k, L entries (the stages)
+    const void* tw_sep;      // real: w(n)^k, L + 1 entries (separation / packing); complex: unused
+    long long rows;
+    long long spec_pitch;    // complex numbers between the spectra of consecutive rows; 0 = one spectrum shared by every row
+    int correlate;           // 1: S = conj(H)
+    double scale;            // final factor of the inverse stores (the user's scale, times 1/n when normalising)
+};
+
+template <typename RL, typename Acc = RadixList<>> struct ReverseRadices;
+template <int... A> struct ReverseRadices<RadixList<>, RadixList<A...>> { using type = RadixList<A...>; };
+template <int R, int... Rs, int... A> struct ReverseRadices<RadixList<R, Rs...>, RadixList<A...>> {
+    using type = typename ReverseRadices<RadixList<Rs...>, RadixList<R, A...>>::type;
+};
+
+// The epilogues read, from the row's TileArgs copy, fields no row stage reads: in1 = the row's spectrum, tw_lo = the separation table,
+// has_tw = correlate.
+template <typename T> __device__ __forceinline__ cplx<T> conv_spec(const TileArgs& a, int idx, bool valid) {
+    if (!valid) return cplx<T>{(T)0, (T)0};
+    cplx<T> h = reinterpret_cast<const cplx<T>*>(a.in1)[idx];
+    if (a.has_tw) h.y = -h.y;
+    return h;
+}
+
+// Between two butterflies' worth of spectrum products (real rows: between two points): keeps the scheduler from hoisting every spectrum
+// load of the row above the first product, which would hold PPT more complex numbers live (three times that on the real rows, with the
+// separation twiddles)
+__device__ __forceinline__ void conv_group_fence() { __builtin_amdgcn_sched_barrier(0); }
+
+// The inverse transform of the registers (already in its first-stage layout) with the final stores.  voff: the thread's byte offset
+// within the row (0 where the kernel folded it into outb).
+template <typename T, int L, int W, bool HALF, typename RL, int TPR, typename LdsT>
+__device__ __forceinline__ void conv_inverse(LdsT* lds, cplx<T>* v, const TileArgs& a, int tid, char* outb, bool valid) {
+    using Inv = typename ReverseRadices<RL>::type;
+    TileArgs c = a;
+    c.inverse = 1;
+    const unsigned voff = W > 1 ? 0u : (unsigned)tid * (unsigned)sizeof(cplx<T>);
+    __syncthreads();       // every thread is done with the slab (the forward's last operands, the mirrors): the inverse may spill
+    Row2Stages<T, L, TPR, 1, true, HALF, Inv>::template run<true>(lds, v, c, tid, nullptr, outb, voff, valid);
+}
+
+template <typename T, int L, int W, bool HALF, typename RL> struct ConvEpi {
+    template <int NB, int R, int TPR, int LR, typename LdsT>
+    static __device__ __forceinline__ void run(LdsT* lds, cplx<T>* v, const TileArgs& a, int tid, char* outb, bool valid) {
+        static_assert(FirstRadix<typename ReverseRadices<RL>::type>::value == R, "the inverse starts with the forward's last radix");
+        static_for<NB>([&](auto bb) {
+            static_for<R>([&](auto kk) {
+                constexpr int b = bb, k = kk;
+                v[b * R + k] = cmul<T>(v[b * R + k], conv_spec<T>(a, b * TPR + k * LR + tid, valid));
+            });
+            conv_group_fence();
+        });
+        conv_inverse<T, L, W, HALF, RL, TPR>(lds, v, a, tid, outb, valid);
+    }
+};
+
+// Z'[k] from s = Z[k] + conj Z[L - k], d = Z[k] - conj Z[L - k] (Z the packed forward transform):
+//   X[k] = 1/2 (s - i t), X[L - k] = conj(1/2 (s + i t)), t = w(n)^k d;   Y = X * S;   at k = 0 the pair is X[0], X[L], real parts only
+//   Z'[k] = (Y[k] + conj Y[L - k]) + i conj(w(n)^k) (Y[k] - conj Y[L - k])
+// and the unnormalised inverse transform of Z' is n times the inverse real transform of Y, packed.
+template <typename T, int L>
+__device__ __forceinline__ cplx<T> conv_real_pair(cplx<T> s, cplx<T> d, int idx, const TileArgs& a, bool valid) {
+    const cplx<T> w = reinterpret_cast<const cplx<T>*>(a.tw_lo)[idx];
+    const cplx<T> t = {w.x * d.x - w.y * d.y, w.x * d.y + w.y * d.x};
+    const T h = (T)0.5;
+    cplx<T> y1 = cmul<T>(cplx<T>{(s.x + t.y) * h, (s.y - t.x) * h}, conv_spec<T>(a, idx, valid));
+    cplx<T> y2 = cmul<T>(cplx<T>{(s.x - t.y) * h, -(s.y + t.x) * h}, conv_spec<T>(a, L - idx, valid));
+    if (idx == 0) {
+        y1.y = 0;
+        y2.y = 0;
+    }
+    const cplx<T> sm = {y1.x + y2.x, y1.y - y2.y}, df = {y1.x - y2.x, y1.y + y2.y};
+    const cplx<T> u = {w.x * df.x + w.y * df.y, w.x * df.y - w.y * df.x};     // conj(w) df
+    return cplx<T>{sm.x - u.y, sm.y + u.x};
+}
+
+template <typename T, int L, int W, bool HALF, typename RL> struct ConvRealEpi {
+    template <int NB, int R, int TPR, int LR, typename LdsT>
+    static __device__ __forceinline__ void run(LdsT* lds, cplx<T>* v, const TileArgs& a, int tid, char* outb, bool valid) {
+        static_assert(FirstRadix<typename ReverseRadices<RL>::type>::value == R, "the inverse starts with the forward's last radix");
+        __syncthreads();       // every thread has fetched its last-stage operands: the slab is free
+        if constexpr (!HALF) {
+            static_for<NB>([&](auto bb) {
+                static_for<R>([&](auto kk) {
+                    constexpr int b = bb, k = kk;
+                    lds[row2_pad(b * TPR + k * LR + tid)] = v[b * R + k];
+                });
+            });
+            __syncthreads();
+            static_for<NB>([&](auto bb) {
+                static_for<R>([&](auto kk) {
+                    constexpr int b = bb, k = kk;
+                    const int idx = b * TPR + k * LR + tid;
+                    const cplx<T> p = v[b * R + k], q = lds[row2_pad((L - idx) & (L - 1))];
+                    v[b * R + k] = conv_real_pair<T, L>(cplx<T>{p.x + q.x, p.y - q.y}, cplx<T>{p.x - q.x, p.y + q.y}, idx, a, valid);
+                    conv_group_fence();
+                });
+            });
+        } else {
+            // the slab holds L scalars: real parts, then imaginary parts (RealSepEpi).  After the first round v[i].x holds s.x, dx[i] d.x.
+            T dx[NB * R];
+            static_for<NB>([&](auto bb) {
+                static_for<R>([&](auto kk) {
+                    constexpr int b = bb, k = kk;
+                    lds[row2_pad(b * TPR + k * LR + tid)] = v[b * R + k].x;
+                });
+            });
+            __syncthreads();
+            static_for<NB>([&](auto bb) {
+                static_for<R>([&](auto kk) {
+                    constexpr int b = bb, k = kk;
+                    const int idx = b * TPR + k * LR + tid;
+                    const T qx = lds[row2_pad((L - idx) & (L - 1))];
+                    dx[b * R + k] = v[b * R + k].x - qx;
+                    v[b * R + k].x += qx;
+                });
+            });
+            __syncthreads();
+            static_for<NB>([&](auto bb) {
+                static_for<R>([&](auto kk) {
+                    constexpr int b = bb, k = kk;
+                    lds[row2_pad(b * TPR + k * LR + tid)] = v[b * R + k].y;
+                });
+            });
+            __syncthreads();
+            static_for<NB>([&](auto bb) {
+                static_for<R>([&](auto kk) {
+                    constexpr int b = bb, k = kk;
+                    const int idx = b * TPR + k * LR + tid;
+                    const T qy = lds[row2_pad((L - idx) & (L - 1))];
+                    const T py = v[b * R + k].y;
+                    v[b * R + k] = conv_real_pair<T, L>(cplx<T>{v[b * R + k].x, py - qy}, cplx<T>{dx[b * R + k], py + qy}, idx, a, valid);
+                    conv_group_fence();
+                });
+            });
+        }
+        conv_inverse<T, L, W, HALF, RL, TPR>(lds, v, a, tid, outb, valid);
+    }
+};
+
+// The row's TileArgs: what the stages read (tw_L, inverse, nt, scale) and what the epilogues read (in1, tw_lo, has_tw)
+__device__ __forceinline__ TileArgs conv_tile_args(const ConvRowArgs& a, const void* spec_row) {
+    TileArgs t = {};
+    t.in0 = a.in;
+    t.in1 = spec_row;
+    t.out0 = a.out;
+    t.tw_L = a.tw;
+    t.tw_lo = a.tw_sep;
+    t.total = a.rows;
+    t.has_tw = a.correlate;
+    t.scale = a.scale;
+    return t;
+}
+
+// W rows of L complex (REAL: packed) points per work-group, NT threads; NT == W: one thread per row (L <= 32), both transforms in registers
+template <typename T, int L, int W, int NT, bool HALF, int OCC, typename RL, bool REAL>
+__device__ __forceinline__ void conv_row_body(const ConvRowArgs& a) {
+    constexpr int TPR = NT / W;
+    if constexpr (TPR == 1) {
+        const long long row = (long long)blockIdx.x * NT + threadIdx.x;
+        if (row >= a.rows) return;
+        const cplx<T>* in = reinterpret_cast<const cplx<T>*>(a.in) + row * L;
+        cplx<T>* out = reinterpret_cast<cplx<T>*>(a.out) + row * L;
+        const TileArgs t = conv_tile_args(a, reinterpret_cast<const cplx<T>*>(a.spec) + row * a.spec_pitch);
+        cplx<T> v[L];
+        static_for<L>([&](auto k) { v[k] = in[k]; });
+        Dft<L, T>::run(v);
+        if constexpr (!REAL) {
+            static_for<L>([&](auto k) {
+                const cplx<T> y = cmul<T>(v[k], conv_spec<T>(t, k, true));
+                v[k] = cplx<T>{y.x, -y.y};
+            });
+        } else {
+            cplx<T> z[L];
+            static_for<L>([&](auto kk) {
+                constexpr int k = kk;
+                const cplx<T> p = v[k], q = v[(L - k) & (L - 1)];
+                const cplx<T> y = conv_real_pair<T, L>(cplx<T>{p.x + q.x, p.y - q.y}, cplx<T>{p.x - q.x, p.y + q.y}, k, t, true);
+                z[k] = cplx<T>{y.x, -y.y};
+            });
+            static_for<L>([&](auto k) { v[k] = z[k]; });
+        }
+        Dft<L, T>::run(v);        // the conjugate's forward transform
+        const T sc = (T)a.scale;
+        static_for<L>([&](auto k) { out[k] = cplx<T>{v[k].x * sc, -v[k].y * sc}; });
+    } else {
+        constexpr int PPT = L / TPR;
+        constexpr int LP = L + L / 16;
+        static_assert(TPR * W == NT && PPT * TPR == L && L >= 16, "bad row configuration");
+        using LdsT = typename std::conditional<HALF, T, cplx<T>>::type;
+        __shared__ __attribute__((aligned(16))) LdsT lds[W * LP];
+        const int c = W == 1 ? 0 : threadIdx.x / TPR, u = W == 1 ? threadIdx.x : threadIdx.x % TPR;
+        const long long row = (long long)blockIdx.x * W + c;
+        const bool valid = row < a.rows;
+        const TileArgs t = conv_tile_args(a, reinterpret_cast<const cplx<T>*>(a.spec) + (valid ? row * a.spec_pitch : 0));
+        const char* inb = reinterpret_cast<const char*>(reinterpret_cast<const cplx<T>*>(a.in) + row * L);
+        char* outb = reinterpret_cast<char*>(reinterpret_cast<cplx<T>*>(a.out) + row * L);
+        unsigned voff = (unsigned)u * (unsigned)sizeof(cplx<T>);
+        if constexpr (W > 1) {  // the row differs across the wave: fold the thread's offset into its own 64-bit base
+            inb += voff;
+            outb += voff;
+            voff = 0;
+        }
+        using Epi = typename std::conditional<REAL, ConvRealEpi<T, L, W, HALF, RL>, ConvEpi<T, L, W, HALF, RL>>::type;
+        cplx<T> v[PPT];
+        Row2Stages<T, L, TPR, 1, true, HALF, RL, 0, Epi>::run(lds + c * LP, v, t, u, inb, outb, voff, valid);
+    }
+}
+
+template <typename T, int L, int W, int NT, bool HALF, int OCC, typename RL>
+__global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(OCC))) conv_row_kernel(const ConvRowArgs a) {
+    conv_row_body<T, L, W, NT, HALF, OCC, RL, false>(a);
+}
+
+template <typename T, int L, int W, int NT, bool HALF, int OCC, typename RL>
+__global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(OCC))) conv_row_real_kernel(const ConvRowArgs a) {
+    conv_row_body<T, L, W, NT, HALF, OCC, RL, true>(a);
+}
+
+// real != 0: L packed points (n = 2L reals); 0 launched (query: a kernel exists), -2 none, -1 grid too large
+template <typename T, int L, int W, int NT, typename RL, bool HALF = false, int OCC = 1>
+static inline int launch_conv_row(int real, const ConvRowArgs* a, hipStream_t s, int query_only) {
+    if (query_only) return 0;
+    const long long tiles = (a->rows + W - 1) / W;
+    if (tiles <= 0) return 0;
+    if (tiles > 2147483647ll) return -1;
+    if (real) hipLaunchKernelGGL((conv_row_real_kernel<T, L, W, NT, HALF, OCC, RL>), dim3((unsigned)tiles), dim3(NT), 0, s, *a);
+    else hipLaunchKernelGGL((conv_row_kernel<T, L, W, NT, HALF, OCC, RL>), dim3((unsigned)tiles), dim3(NT), 0, s, *a);
+    return (int)hipGetLastError();
+}
+
+// L <= 32: one thread per row
+template <typename T, int L>
+static inline int launch_conv_row_small(int real, const ConvRowArgs* a, hipStream_t s, int query_only) {
+    return launch_conv_row<T, L, 256, 256, RadixList<L>>(real, a, s, query_only);
+}
+
+}  // namespace mifft

@@ -33,6 +33,9 @@ int mifft_fusedx_f64(int L0, int L1, const mifft::FusedArgs* f, unsigned grid, h
 int mifft_fused3_f64_launch(int L0, int L1, const mifft::FusedArgs* f, int split, unsigned grid, hipStream_t s);
 int mifft_aux_copy_launch(const struct mifft_copy* c, const void* s0, const void* s1, void* d0, void* d1, hipStream_t s);
 int mifft_aux_mul_rows_launch(int f64, void* a, const void* b, long long rows, long long n, hipStream_t s);
+// data[i][j] = scale * data[i][j] * S[i * spectrum_pitch + j] (S = conj(spectrum) when correlate); 0 launched, -1 grid too large
+int mifft_aux_mul_spectrum_launch(int f64, void* data, const void* spectrum, long long items, long long points, long long spectrum_pitch,
+                                  int correlate, double scale, hipStream_t s);
 int mifft_aux_mismatch_launch(const void* a, const void* b, unsigned long long words, unsigned long long* count, hipStream_t s);
 int mifft_aux_zero_launch(void* p, unsigned long long nbytes, hipStream_t s);     // nbytes a multiple of 16, p 16-byte aligned
 int mifft_wave_supported(int f64, int N);
@@ -70,6 +73,11 @@ int mifft_real_post_launch(int f64, int inverse, int nx, int ny, int nz, long lo
 // fft_real_row_f32.hip / _f64.hip: one-launch real rows of L = n / 2 packed points; 0 launched (query: a kernel exists), -2 none, -1 grid too large
 int mifft_real_row_dispatch_f32(int L, int inverse, const mifft::TileArgs* a, hipStream_t s, int query_only);
 int mifft_real_row_dispatch_f64(int L, int inverse, const mifft::TileArgs* a, hipStream_t s, int query_only);
+// fft_conv_f32.hip / _f64.hip: one-launch convolution rows of L complex (real: packed) points; 0 launched (query: a kernel exists), -2 none,
+// -1 grid too large
+namespace mifft { struct ConvRowArgs; }
+int mifft_conv_row_dispatch_f32(int real, int L, const mifft::ConvRowArgs* a, hipStream_t s, int query_only);
+int mifft_conv_row_dispatch_f64(int real, int L, const mifft::ConvRowArgs* a, hipStream_t s, int query_only);
 // fft_nd2z.hip: 0 = launched (query 1: a kernel exists; query 2: one that is preferred at every buffer size), -2 = none, -1 = grid too large
 int mifft_nd2z(int f64, int x, int y, int z, const mifft::TileArgs* a, hipStream_t s, int query);
 // fft_half.hip / fft_nd2_c32_*.hip: complex32 twins of the fp32 one-launch kernels; 0 launched (query: a kernel exists), -2 none, -1 grid too large

@@ -12,6 +12,7 @@
 
 #include "../../include/mifft.h"
 #include "mifft_internal.h"
+#include "fft_conv_row.hpp"
 
 namespace {
 
@@ -1400,6 +1401,72 @@ int mifft_launch_real_row(int32_t precision, int32_t n, int32_t inverse, int64_t
     const int rc = precision == MIFFT_F64 ? mifft_real_row_dispatch_f64((int)L, inverse, &a, (hipStream_t)stream, 0)
                                           : mifft_real_row_dispatch_f32((int)L, inverse, &a, (hipStream_t)stream, 0);
     if (rc == -2) return set_err(MIFFT_E_UNSUPPORTED, "real row: no kernel for n = %d", n);
+    if (rc == -1) return set_err(MIFFT_E_INVALID, "grid too large");
+    if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
+    return 0;
+}
+// convolution rows (fft_conv_row.hpp): complex rows of n points (L = n), real rows of n reals (L = n / 2 packed points)
+int mifft_conv_row_supported(int32_t precision, int32_t real, int32_t n) {
+    if ((precision != MIFFT_F32 && precision != MIFFT_F64) || (real != 0 && real != 1) || n < 2 || !is_pow2(n)) return MIFFT_E_UNSUPPORTED;
+    if (real && n < 4) return MIFFT_E_UNSUPPORTED;
+    const int L = real ? n / 2 : n;
+    const int rc = precision == MIFFT_F64 ? mifft_conv_row_dispatch_f64(real, L, nullptr, nullptr, 1)
+                                          : mifft_conv_row_dispatch_f32(real, L, nullptr, nullptr, 1);
+    return rc == 0 ? 0 : MIFFT_E_UNSUPPORTED;
+}
+int mifft_launch_conv_row(int32_t precision, int32_t real, int32_t n, int64_t rows, const void* in, void* out, const void* spectrum,
+                          int64_t spectrum_pitch, int32_t correlate, const void* tw, const void* tw_sep, double scale, mifft_stream_t stream) {
+    if (precision != MIFFT_F32 && precision != MIFFT_F64) return set_err(MIFFT_E_INVALID, "conv row: bad precision %d", precision);
+    if (real != 0 && real != 1) return set_err(MIFFT_E_INVALID, "conv row: real must be 0 or 1");
+    if (n < 2 || !is_pow2(n)) return set_err(MIFFT_E_INVALID, "conv row: n = %d is not a power of two >= 2", n);
+    if (mifft_conv_row_supported(precision, real, n) != 0) return set_err(MIFFT_E_UNSUPPORTED, "conv row: no kernel for n = %d", n);
+    if (correlate != 0 && correlate != 1) return set_err(MIFFT_E_INVALID, "conv row: correlate must be 0 or 1");
+    if (rows < 0) return set_err(MIFFT_E_INVALID, "conv row: negative row count");
+    if (!in || !out || !spectrum || !tw || (real && !tw_sep)) return set_err(MIFFT_E_INVALID, "conv row: null buffer");
+    const long long esz = precision == MIFFT_F64 ? 16 : 8;
+    if (((uintptr_t)in | (uintptr_t)out | (uintptr_t)spectrum | (uintptr_t)tw | (uintptr_t)tw_sep) & (uintptr_t)(esz - 1))
+        return set_err(MIFFT_E_INVALID, "conv row: buffers must be aligned to one complex number");
+    const long long L = real ? n / 2 : n, sp = real ? L + 1 : L;
+    if (spectrum_pitch != 0 && spectrum_pitch < sp)
+        return set_err(MIFFT_E_INVALID, "conv row: spectrum_pitch %lld is neither 0 (shared) nor at least %lld", (long long)spectrum_pitch, sp);
+    if (mul3_checked(rows, L, esz) < 0 || mul3_checked(rows, spectrum_pitch > sp ? spectrum_pitch : sp, esz) < 0)
+        return set_err(MIFFT_E_INVALID, "conv row: rows * n overflows");
+    if (rows == 0) return 0;
+    const uintptr_t i0 = (uintptr_t)in, i1 = i0 + (uintptr_t)(rows * L * esz);
+    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (uintptr_t)(rows * L * esz);
+    if (i0 != o0 && i0 < o1 && o0 < i1) return set_err(MIFFT_E_INVALID, "conv row: input and output overlap without being equal");
+    const uintptr_t s0 = (uintptr_t)spectrum,
+                    s1 = s0 + (uintptr_t)(((spectrum_pitch ? (rows - 1) * spectrum_pitch : 0) + sp) * esz);
+    if ((s0 < i1 && i0 < s1) || (s0 < o1 && o0 < s1)) return set_err(MIFFT_E_INVALID, "conv row: the spectrum overlaps the data");
+    mifft::ConvRowArgs a = {};
+    a.in = in;
+    a.out = out;
+    a.spec = spectrum;
+    a.tw = tw;
+    a.tw_sep = tw_sep;
+    a.rows = rows;
+    a.spec_pitch = spectrum_pitch;
+    a.correlate = correlate;
+    a.scale = scale;
+    const int rc = precision == MIFFT_F64 ? mifft_conv_row_dispatch_f64(real, (int)L, &a, (hipStream_t)stream, 0)
+                                          : mifft_conv_row_dispatch_f32(real, (int)L, &a, (hipStream_t)stream, 0);
+    if (rc == -2) return set_err(MIFFT_E_UNSUPPORTED, "conv row: no kernel for n = %d", n);
+    if (rc == -1) return set_err(MIFFT_E_INVALID, "grid too large");
+    if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
+    return 0;
+}
+int mifft_aux_mul_spectrum(int32_t precision, void* data, const void* spectrum, int64_t items, int64_t points, int64_t spectrum_pitch,
+                           int32_t correlate, double scale, mifft_stream_t stream) {
+    if (precision != MIFFT_F32 && precision != MIFFT_F64) return set_err(MIFFT_E_INVALID, "mul_spectrum: bad precision %d", precision);
+    if (!data || !spectrum) return set_err(MIFFT_E_INVALID, "mul_spectrum: null buffer");
+    if (items < 0 || points < 1 || (spectrum_pitch != 0 && spectrum_pitch < points) || (correlate != 0 && correlate != 1))
+        return set_err(MIFFT_E_INVALID, "mul_spectrum: bad arguments");
+    const long long esz = precision == MIFFT_F64 ? 16 : 8;
+    if (((uintptr_t)data | (uintptr_t)spectrum) & (uintptr_t)(esz - 1))
+        return set_err(MIFFT_E_INVALID, "mul_spectrum: buffers must be aligned to one complex number");
+    if (mul3_checked(items, points, esz) < 0) return set_err(MIFFT_E_INVALID, "mul_spectrum: items * points overflows");
+    const int rc = mifft_aux_mul_spectrum_launch(precision == MIFFT_F64, data, spectrum, items, points, spectrum_pitch, correlate, scale,
+                                                 (hipStream_t)stream);
     if (rc == -1) return set_err(MIFFT_E_INVALID, "grid too large");
     if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
     return 0;

@@ -591,6 +591,13 @@ def Plan(*args, **kwds):
     execute(real_in, spectrum_out) / execute(spectrum_in, real_out, inverse=True), out of place, numpy's rfftn / irfftn layout.
     `dtype="complex32"` (or torch.complex32): half-precision transforms (pyfft_amd/half.py): interleaved fp16 data, fp32 arithmetic, one
     rounding to fp16 at the store; the one-launch shapes of complex64 only.  numpy.float16 (split half planes) is a ValueError.
+    `convolve=True`: convolution plans (pyfft_amd/conv.py): execute(x, y, spectrum=H, batch=k, correlate=False, spectrum_batch=1) computes
+    y = scale * IFFTN(FFTN(x) * S) per item, S = H, or conj(H) with correlate=True; IFFTN divides by the item's point count only when
+    normalize=True, and scale multiplies the result once.  H: a device buffer of interleaved complex numbers in the plan's precision, `shape`
+    points (real=True: numpy's rfftn half spectrum, spectrum_shape(shape) points), shared by every item or one per item
+    (spectrum_batch=batch).  y may be x (in place).  With real=True, y == numpy.fft.irfftn(numpy.fft.rfftn(x) * S, s=shape) * scale (numpy's
+    edge-plane rule).  filter_spectrum(h, H) computes H = fftn(h) (rfftn), scale 1.  complex64 / complex128 or real=True float32 / float64;
+    complex32, split planes, any_size= and parent_shape= are ValueErrors.
     `parent_shape=`, `any_size=True`: opt-in extensions (tiles of a bigger array; sizes that are not powers of two), see
     pyfft_amd/generic.py.  Without them a size that is not a power of two is a ValueError, as in the reference.
     `fast_math`: accepted for signature parity and ignored -- the reference passes -use_fast_math to nvcc for its on-device
@@ -605,12 +612,21 @@ def Plan(*args, **kwds):
     any_size = bool(kwds.pop('any_size', False))
     # opt-in real-input transforms (pyfft_amd/real.py): dtype names the real precision, the spectrum is numpy's rfftn half spectrum
     real = bool(kwds.pop('real', False))
+    # opt-in convolution plans (pyfft_amd/conv.py): execute(x, y, spectrum=H) = scale * IFFTN(FFTN(x) * H)
+    convolve = bool(kwds.pop('convolve', False))
+    if convolve:
+        if parent_shape is not None or any_size:
+            raise ValueError("pyfft_amd: convolve=True cannot be combined with any_size= or parent_shape=")
+        from .conv import ConvPlan
+        ConvPlan.validate(*args, real=real, **kwds)
     if real and (parent_shape is not None or any_size):
         raise ValueError("pyfft_amd: real=True cannot be combined with any_size= or parent_shape=")
     # complex32 (pyfft_amd/half.py): routed before FFTPlan.validate, which knows no half dtype
     from .half import HalfFFTPlan, is_complex32, is_float16
     dtype = args[1] if len(args) > 1 else kwds.get('dtype')
     half = is_complex32(dtype)
+    if convolve and half:
+        raise ValueError("pyfft_amd: convolve=True has no complex32 form")
     if is_float16(dtype) and not real and parent_shape is None and not any_size:
         raise ValueError("pyfft_amd: float16 would mean split half planes, which do not exist: only interleaved complex32 "
                          "(dtype=\"complex32\" or torch.complex32) has half-precision transforms")
@@ -627,7 +643,9 @@ def Plan(*args, **kwds):
             pass
 
     # argument errors first (ValueError, as in the reference), then the device
-    if half:
+    if convolve:
+        pass                # (validated above)
+    elif half:
         HalfFFTPlan.validate(*args, **kwds)
     elif real:
         from .real import RealFFTPlan
@@ -659,6 +677,9 @@ def Plan(*args, **kwds):
     context = Context(device, stream_obj, mempool)
     prev = context.activate()       # context=i: tables and scratch are allocated on device i
     try:
+        if convolve:
+            from .conv import ConvPlan
+            return ConvPlan(context, *args, real=real, **kwds)
         if half:
             return HalfFFTPlan(context, *args, **kwds)
         if real:
