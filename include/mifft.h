@@ -521,6 +521,47 @@ int mifft_launch_conv_row(int32_t precision, int32_t real, int32_t n, int64_t ro
 int mifft_aux_mul_spectrum(int32_t precision, void *data, const void *spectrum, int64_t items, int64_t points, int64_t spectrum_pitch,
                            int32_t correlate, double scale, mifft_stream_t stream);
 
+/* Cosine and sine transforms (docs/extensions.md "Real-to-real transforms"): DCT-II / DST-II forward and DCT-III / DST-III inverse
+ * (scipy.fft's type 2 and 3) by Makhoul's algorithm, composed as pre step -> complex transform of the packed data -> post step.  An
+ * item is a dense real array of shape n[0 .. ndim - 1] (numpy order, the last axis contiguous; every axis a power of two >= 2); v, its
+ * per-axis permutation [x0, x2, x4, ..., x5, x3, x1] (DST: x[j] signed by (-1)^(sum of its indices) first), read as interleaved complex
+ * numbers is the packed array z of shape (..., n_last / 2), the same bytes.
+ *   mifft_launch_r2r_pre   inverse 0: in = x -> out = scale * v  (the permutation; ndim 1 with n[0] = 1 is a one-point item, in == out
+ *                                     allowed)
+ *                          inverse 1: in = Y -> out = Z' with IFFT(Z') (unnormalised) = the type III transform's packed v, times the
+ *                                     factor the tables carry
+ *   mifft_launch_r2r_post  inverse 0: in = Z = FFT(z) -> out = Y, the type II transform times the factor the tables carry
+ *                          inverse 1: in = v -> out = scale * x  (the inverse permutation; the one-point item as above)
+ * tw (the twiddle steps only): the per-axis tables in axis order, n[a] entries each -- forward t[k] = c[k] w(4n)^k, inverse
+ * u[k] = w(4n)^-k / (2 c[k]), c the ortho weight or 1, the last axis's times the global factor (forward: 1/2 for the separation) --
+ * followed by w(n_last)^k, k = 0 .. n_last / 4 (n_last / 4 + 1 entries; 1 for n_last = 2), the precision's complex type.
+ * kind 0 DCT, 1 DST (Y read / written backwards on every axis).  Items dense on both sides; in and out must not overlap; real buffers
+ * aligned to one real number, the packed side and tw to one complex number. */
+typedef struct mifft_r2r_step {
+    int32_t precision;   /* MIFFT_F32 / MIFFT_F64 */
+    int32_t inverse;     /* 0 forward (type II), 1 inverse (type III) */
+    int32_t kind;        /* 0 DCT, 1 DST */
+    int32_t ndim;        /* 1 .. 3 */
+    int32_t n[3];        /* the item's axes, numpy order */
+    int32_t reserved;    /* 0 */
+    int64_t outer;       /* items */
+    const void *in;
+    void *out;
+    const void *tw;
+    double scale;        /* the permutation steps' factor */
+} mifft_r2r_step;
+int mifft_launch_r2r_pre(const mifft_r2r_step *desc, mifft_stream_t stream);
+int mifft_launch_r2r_post(const mifft_r2r_step *desc, mifft_stream_t stream);
+/* One-launch cosine / sine rows: `rows` dense rows of n reals, forward y = the type II transform times the factor tab carries,
+ * inverse x = the type III transform likewise (the same algorithm as the steps above, in one work-group: the row crosses HBM once).
+ * tw_stage = w(n/2)^k (n/2 entries), tw_sep = w(n)^k (n/2 entries), tab = forward t'[k] = 2 g c[k] w(4n)^k (n/2 + 1 entries) or inverse
+ * u[k] = g w(4n)^-k / 2c[k] (n entries), g the factor, c the ortho weight or 1; the precision's complex type.  kind 0 DCT, 1 DST.  in == out
+ * (in place) or disjoint; in and out 16-byte aligned.
+ *   mifft_r2r_row_supported   0 if a kernel exists for the real length n (4 ... 8192, fp32 and fp64), else MIFFT_E_UNSUPPORTED */
+int mifft_r2r_row_supported(int32_t precision, int32_t n);
+int mifft_launch_r2r_row(int32_t precision, int32_t n, int32_t inverse, int32_t kind, int64_t rows, const void *in, void *out,
+                         const void *tw_stage, const void *tw_sep, const void *tab, mifft_stream_t stream);
+
 /* Half-precision (complex32) transforms (docs/extensions.md "Half-precision transforms"): interleaved fp16 data, one fp16 real and one
  * fp16 imaginary part per point (4 bytes).  Loads widen to fp32 exactly, every stage runs in fp32 on the fp32 twiddle tables, and the
  * result (times scale, in fp32) is rounded to fp16 once, to nearest even, at the store: beyond +-65504 it is +-inf, NaN stays NaN.

@@ -131,6 +131,23 @@ class MifftFusedSync(ctypes.Structure):
     ]
 
 
+class MifftR2rStep(ctypes.Structure):
+    """struct mifft_r2r_step (include/mifft.h): a pre / post step of a cosine or sine transform."""
+    _fields_ = [
+        ("precision", ctypes.c_int32),
+        ("inverse", ctypes.c_int32),
+        ("kind", ctypes.c_int32),
+        ("ndim", ctypes.c_int32),
+        ("n", ctypes.c_int32 * 3),
+        ("reserved", ctypes.c_int32),
+        ("outer", ctypes.c_int64),
+        ("in_", ctypes.c_void_p),
+        ("out", ctypes.c_void_p),
+        ("tw", ctypes.c_void_p),
+        ("scale", ctypes.c_double),
+    ]
+
+
 class MifftRealPost(ctypes.Structure):
     """struct mifft_real_post (include/mifft.h): the separation / packing step of a real-input transform."""
     _fields_ = [
@@ -233,6 +250,10 @@ PROTOTYPES = {
     "mifft_conv_row_supported": (ctypes.c_int, [_i32, _i32, _i32]),
     "mifft_launch_conv_row": (ctypes.c_int, [_i32, _i32, _i32, ctypes.c_int64, _vp, _vp, _vp, ctypes.c_int64, _i32, _vp, _vp, ctypes.c_double, _vp]),
     "mifft_aux_mul_spectrum": (ctypes.c_int, [_i32, _vp, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _i32, ctypes.c_double, _vp]),
+    "mifft_launch_r2r_pre": (ctypes.c_int, [ctypes.POINTER(MifftR2rStep), _vp]),
+    "mifft_launch_r2r_post": (ctypes.c_int, [ctypes.POINTER(MifftR2rStep), _vp]),
+    "mifft_r2r_row_supported": (ctypes.c_int, [_i32, _i32]),
+    "mifft_launch_r2r_row": (ctypes.c_int, [_i32, _i32, _i32, _i32, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mifft_half_supported": (ctypes.c_int, [_i32, _i32, _i32]),
     "mifft_half_kernel": (ctypes.c_int, [_i32, _i32, _i32, _i32]),
     "mifft_launch_half": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _vp]),

@@ -67,6 +67,13 @@ int mifft_mixed_nd_launch(int f64, int nx, int ny, int nz, long long transforms,
                           const void* twz, int flags, double scale, hipStream_t s);
 int mifft_bluestein_launch(int f64, int n, int m, long long rows, long long stride_in, long long stride_out, const void* in, void* out,
                            const void* tw, const void* chirp, const void* bhat, int flags, double scale, hipStream_t s);
+// fft_r2r.hip: the pre / post steps of the cosine and sine transforms; 0 launched, -1 grid too large, else a hipError_t
+int mifft_r2r_step_launch(int f64, int post, int inverse, int kind, int nd, const int* n, long long outer, const void* in, void* out,
+                          const void* tw, double scale, hipStream_t s);
+// fft_r2r_f32.hip / _f64.hip: one-launch cosine / sine rows of L = n / 2 packed points; 0 launched (query: a kernel exists), -2 none,
+// -1 grid too large
+int mifft_r2r_row_dispatch_f32(int L, int inverse, const mifft::TileArgs* a, hipStream_t s, int query_only);
+int mifft_r2r_row_dispatch_f64(int L, int inverse, const mifft::TileArgs* a, hipStream_t s, int query_only);
 // fft_real.hip: separation / packing step of the real-input transforms; 0 launched, -1 grid too large, else a hipError_t
 int mifft_real_post_launch(int f64, int inverse, int nx, int ny, int nz, long long outer, long long stride_in, long long stride_out,
                            const void* in, void* out, const void* tw, double scale, hipStream_t s);

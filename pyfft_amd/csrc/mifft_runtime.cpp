@@ -1471,6 +1471,86 @@ int mifft_aux_mul_spectrum(int32_t precision, void* data, const void* spectrum, 
     if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
     return 0;
 }
+// cosine and sine transforms (fft_r2r.hip): the steps around the complex transform of the packed data
+static int r2r_step(const mifft_r2r_step* d, int post, mifft_stream_t stream) {
+    const char* what = post ? "r2r post" : "r2r pre";
+    if (!d) return set_err(MIFFT_E_INVALID, "%s: null descriptor", what);
+    if (d->precision != MIFFT_F32 && d->precision != MIFFT_F64) return set_err(MIFFT_E_INVALID, "%s: bad precision %d", what, d->precision);
+    if (d->inverse != 0 && d->inverse != 1) return set_err(MIFFT_E_INVALID, "%s: inverse must be 0 or 1", what);
+    if (d->kind != 0 && d->kind != 1) return set_err(MIFFT_E_INVALID, "%s: kind must be 0 (DCT) or 1 (DST)", what);
+    if (d->ndim < 1 || d->ndim > 3) return set_err(MIFFT_E_INVALID, "%s: ndim must be 1, 2 or 3", what);
+    if (d->reserved != 0) return set_err(MIFFT_E_INVALID, "%s: reserved field must be 0", what);
+    const bool perm = post == d->inverse;       // forward pre, inverse post: the permutation steps
+    const bool single = perm && d->ndim == 1 && d->n[0] == 1;
+    long long pts = 1;
+    for (int a = 0; a < d->ndim; ++a) {
+        if (!single && (d->n[a] < 2 || !is_pow2(d->n[a])))
+            return set_err(MIFFT_E_INVALID, "%s: axis %d has %d points, not a power of two >= 2", what, a, d->n[a]);
+        pts *= d->n[a];
+    }
+    if (d->outer < 0) return set_err(MIFFT_E_INVALID, "%s: negative item count", what);
+    if (!d->in || !d->out || (!perm && !d->tw)) return set_err(MIFFT_E_INVALID, "%s: null buffer", what);
+    const long long rsz = d->precision == MIFFT_F64 ? 8 : 4;
+    const uintptr_t cmask = (uintptr_t)(2 * rsz - 1), rmask = (uintptr_t)(rsz - 1);
+    // the packed side (v, Z, Z') is whole complex numbers; the user side real numbers
+    const uintptr_t packed = (uintptr_t)(perm ? (d->inverse ? d->in : d->out) : (d->inverse ? d->out : d->in));
+    if ((((uintptr_t)d->in | (uintptr_t)d->out) & rmask) || (!single && (packed & cmask)) || (!perm && ((uintptr_t)d->tw & cmask)))
+        return set_err(MIFFT_E_INVALID, "%s: buffers must be aligned to one real (packed side: one complex) number", what);
+    if (mul3_checked(d->outer, pts, rsz) < 0) return set_err(MIFFT_E_INVALID, "%s: items * points overflows", what);
+    if (d->outer == 0) return 0;
+    const uintptr_t i0 = (uintptr_t)d->in, o0 = (uintptr_t)d->out, bytes = (uintptr_t)(d->outer * pts * rsz);
+    if (!(single && i0 == o0) && i0 < o0 + bytes && o0 < i0 + bytes)
+        return set_err(MIFFT_E_INVALID, "%s: input and output overlap (out of place only)", what);
+    const int n[3] = {d->n[0], d->n[1], d->n[2]};
+    const int rc = mifft_r2r_step_launch(d->precision == MIFFT_F64, post, d->inverse, d->kind, d->ndim, n, d->outer, d->in, d->out, d->tw,
+                                         d->scale, (hipStream_t)stream);
+    if (rc == -1) return set_err(MIFFT_E_INVALID, "grid too large");
+    if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
+    return 0;
+}
+// one-launch cosine / sine rows (fft_r2r_row.hpp): rows of n reals, L = n / 2 packed points
+int mifft_r2r_row_supported(int32_t precision, int32_t n) {
+    if ((precision != MIFFT_F32 && precision != MIFFT_F64) || n < 4 || !is_pow2(n)) return MIFFT_E_UNSUPPORTED;
+    const int rc = precision == MIFFT_F64 ? mifft_r2r_row_dispatch_f64(n / 2, 0, nullptr, nullptr, 1)
+                                          : mifft_r2r_row_dispatch_f32(n / 2, 0, nullptr, nullptr, 1);
+    return rc == 0 ? 0 : MIFFT_E_UNSUPPORTED;
+}
+int mifft_launch_r2r_row(int32_t precision, int32_t n, int32_t inverse, int32_t kind, int64_t rows, const void* in, void* out,
+                         const void* tw_stage, const void* tw_sep, const void* tab, mifft_stream_t stream) {
+    if (precision != MIFFT_F32 && precision != MIFFT_F64) return set_err(MIFFT_E_INVALID, "r2r row: bad precision %d", precision);
+    if (n < 4 || !is_pow2(n)) return set_err(MIFFT_E_INVALID, "r2r row: n = %d is not a power of two >= 4", n);
+    if (mifft_r2r_row_supported(precision, n) != 0) return set_err(MIFFT_E_UNSUPPORTED, "r2r row: no kernel for n = %d", n);
+    if (inverse != 0 && inverse != 1) return set_err(MIFFT_E_INVALID, "r2r row: inverse must be 0 or 1");
+    if (kind != 0 && kind != 1) return set_err(MIFFT_E_INVALID, "r2r row: kind must be 0 (DCT) or 1 (DST)");
+    if (rows < 0) return set_err(MIFFT_E_INVALID, "r2r row: negative row count");
+    if (!in || !out || !tw_stage || !tw_sep || !tab) return set_err(MIFFT_E_INVALID, "r2r row: null buffer");
+    const long long rsz = precision == MIFFT_F64 ? 8 : 4;
+    if ((((uintptr_t)in | (uintptr_t)out) & 15) || (((uintptr_t)tw_stage | (uintptr_t)tw_sep | (uintptr_t)tab) & (uintptr_t)(2 * rsz - 1)))
+        return set_err(MIFFT_E_INVALID, "r2r row: data must be 16-byte aligned, tables aligned to one complex number");
+    if (mul3_checked(rows, n, rsz) < 0) return set_err(MIFFT_E_INVALID, "r2r row: rows * n overflows");
+    if (rows == 0) return 0;
+    const uintptr_t i0 = (uintptr_t)in, o0 = (uintptr_t)out, bytes = (uintptr_t)(rows * n * rsz);
+    if (i0 != o0 && i0 < o0 + bytes && o0 < i0 + bytes)
+        return set_err(MIFFT_E_INVALID, "r2r row: input and output overlap without being the same buffer");
+    mifft::TileArgs a = {};
+    a.in0 = in;
+    a.out0 = out;
+    a.tw_L = tw_stage;
+    a.tw_lo = tw_sep;
+    a.tw_hi = tab;
+    a.has_tw = kind;
+    a.total = rows;
+    a.inverse = inverse;
+    a.scale = 1.0;
+    const int rc = precision == MIFFT_F64 ? mifft_r2r_row_dispatch_f64(n / 2, inverse, &a, (hipStream_t)stream, 0)
+                                          : mifft_r2r_row_dispatch_f32(n / 2, inverse, &a, (hipStream_t)stream, 0);
+    if (rc == -2) return set_err(MIFFT_E_UNSUPPORTED, "r2r row: no kernel for n = %d", n);
+    if (rc == -1) return set_err(MIFFT_E_INVALID, "grid too large");
+    if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
+    return 0;
+}
+int mifft_launch_r2r_pre(const mifft_r2r_step* desc, mifft_stream_t stream) { return r2r_step(desc, 0, stream); }
+int mifft_launch_r2r_post(const mifft_r2r_step* desc, mifft_stream_t stream) { return r2r_step(desc, 1, stream); }
 // complex32 transforms: the one-launch shape set of interleaved fp32 data (1-D rows up to 32768 points, the N-D shapes of
 // mifft_nd_shape_supported with MIFFT_VARIANT_INTERLEAVED_ONLY), unit axes taken as given
 int mifft_half_supported(int32_t x, int32_t y, int32_t z) {

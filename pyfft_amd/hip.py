@@ -598,6 +598,10 @@ def Plan(*args, **kwds):
     (spectrum_batch=batch).  y may be x (in place).  With real=True, y == numpy.fft.irfftn(numpy.fft.rfftn(x) * S, s=shape) * scale (numpy's
     edge-plane rule).  filter_spectrum(h, H) computes H = fftn(h) (rfftn), scale 1.  complex64 / complex128 or real=True float32 / float64;
     complex32, split planes, any_size= and parent_shape= are ValueErrors.
+    `r2r="dct"` / `"dst"`: cosine / sine transforms (pyfft_amd/r2r.py): float32 / float64 real data, prod(shape) per item; execute(x, y)
+    == scipy.fft.dctn(x, type=2) * scale (dstn for "dst"), execute(y, x, inverse=True) == idctn(y, type=2) / scale (normalize=False:
+    dctn(y, type=3) / scale); `ortho=True` is norm="ortho" both ways; y may be x (in place).  Complex dtypes, real=, convolve=, any_size=
+    and parent_shape= are ValueErrors.
     `parent_shape=`, `any_size=True`: opt-in extensions (tiles of a bigger array; sizes that are not powers of two), see
     pyfft_amd/generic.py.  Without them a size that is not a power of two is a ValueError, as in the reference.
     `fast_math`: accepted for signature parity and ignored -- the reference passes -use_fast_math to nvcc for its on-device
@@ -614,6 +618,13 @@ def Plan(*args, **kwds):
     real = bool(kwds.pop('real', False))
     # opt-in convolution plans (pyfft_amd/conv.py): execute(x, y, spectrum=H) = scale * IFFTN(FFTN(x) * H)
     convolve = bool(kwds.pop('convolve', False))
+    # opt-in cosine / sine transforms (pyfft_amd/r2r.py): r2r="dct" | "dst", ortho=True for norm="ortho"
+    r2r = kwds.pop('r2r', None)
+    if r2r is not None:
+        if real or convolve or any_size or parent_shape is not None:
+            raise ValueError("pyfft_amd: r2r= cannot be combined with real=, convolve=, any_size= or parent_shape=")
+        from .r2r import R2RPlan
+        R2RPlan.validate(*args, r2r=r2r, **kwds)
     if convolve:
         if parent_shape is not None or any_size:
             raise ValueError("pyfft_amd: convolve=True cannot be combined with any_size= or parent_shape=")
@@ -643,7 +654,7 @@ def Plan(*args, **kwds):
             pass
 
     # argument errors first (ValueError, as in the reference), then the device
-    if convolve:
+    if convolve or r2r is not None:
         pass                # (validated above)
     elif half:
         HalfFFTPlan.validate(*args, **kwds)
@@ -680,6 +691,8 @@ def Plan(*args, **kwds):
         if convolve:
             from .conv import ConvPlan
             return ConvPlan(context, *args, real=real, **kwds)
+        if r2r is not None:
+            return R2RPlan(context, *args, r2r=r2r, **kwds)
         if half:
             return HalfFFTPlan(context, *args, **kwds)
         if real:

@@ -87,6 +87,8 @@ class ShardedPlan(object):
         for key in ("context", "stream"):
             if key in plan_kwds:
                 raise ValueError("ShardedPlan sets %s= per shard" % key)
+        if "r2r" in plan_kwds:
+            raise ValueError("ShardedPlan has no r2r= (cosine / sine transform) form")
         self._wait_for_finish = plan_kwds.pop("wait_for_finish", None)
         if self._wait_for_finish is None:
             self._wait_for_finish = True
