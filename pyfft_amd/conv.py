@@ -146,6 +146,18 @@ class ConvPlan(object):
         for d in (xs, ys):
             if ss < d + data_bytes and d < ss + spec_bytes:
                 raise ValueError("pyfft_amd: convolve plan spectrum overlaps the data")
+        # bases, refused here before anything is enqueued: the data as every launch that touches it takes it (the one-launch row: one
+        # complex number; the inner complex plan: 16 bytes; the inner real plan: its real_side_alignment), the spectrum one complex number
+        cs = self._cdtype.itemsize
+        if self.conv_form == "fused_row":
+            need = cs
+        elif self._real:
+            need = self._inner.real_side_alignment
+        else:
+            need = 16
+        if xs % need or ys % need or ss % cs:
+            raise ValueError("pyfft_amd: convolve plan bases must be aligned: the data to %d bytes, the spectrum to %d (one complex number)"
+                             % (need, cs))
         return xs, ys, ss
 
     @on_plan_device

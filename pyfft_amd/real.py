@@ -174,6 +174,13 @@ class RealFFTPlan(object):
         n_out = batch * (self._size * rs if inverse else self._spec_points * cs)
         if src < dst + n_out and dst < src + n_in:
             raise ValueError("pyfft_amd: real plans are out of place only (input and output must not overlap)")
+        # bases, refused here before anything is enqueued (an inverse used to enqueue its packing launch before the inner plan refused
+        # the real side): the real side as real_side_alignment says, the spectrum one complex number
+        real_ptr, spec_ptr = (dst, src) if inverse else (src, dst)
+        need = self.real_side_alignment
+        if real_ptr % need or spec_ptr % cs:
+            raise ValueError("pyfft_amd: real plan bases must be aligned: the real side to %d bytes, the spectrum to %d (one complex "
+                             "number)" % (need, cs))
         ctx.createQueue((data_in, data_out))
         wait = self._wait_for_finish if wait_for_finish is None else wait_for_finish
         capturing = ctx.capturing()
@@ -262,6 +269,12 @@ class RealFFTPlan(object):
     @property
     def inner_plan(self):
         return self._inner
+
+    @property
+    def real_side_alignment(self):
+        """Bytes the base of the real side must be aligned to: 16 where the inner complex plan reads or writes it, one complex number
+        where the one-launch row or the packing launch alone does (the spectrum side always takes one complex number)."""
+        return 16 if self._inner is not None else self._cdtype.itemsize
 
     def spectrum_shape(self):
         return spectrum_shape(self._shape)

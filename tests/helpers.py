@@ -298,8 +298,9 @@ def check_accuracy(shape, dtype, batch, input_of, output_of, inverse=False, norm
 
 
 class GuardedBuffer(object):
-    """A user range of `nbytes` inside ONE device allocation: it starts `offset` bytes past a 64 KiB front guard (`offset` 16-byte
-    aligned: the C ABI's requirement; not 64-byte aligned, unlike every hipMalloc base) and is followed by a back guard of at least
+    """A user range of `nbytes` inside ONE device allocation: it starts `offset` bytes past a 64 KiB front guard (`offset` a multiple
+    of `align`: 16 by default, the C ABI's requirement for most entry points; an element-aligned run passes the element's size; not
+    64-byte aligned, unlike every hipMalloc base) and is followed by a back guard of at least
     1 MiB, larger than any tile.  Both guards hold a quiet NaN with a recognisable payload in either precision, so that a kernel writing
     or reading out of its range lands in memory the test owns: check_guards() copies back the guard bytes alone and asserts that they
     are bit-identical to what was written."""
@@ -308,10 +309,10 @@ class GuardedBuffer(object):
     BACK = 1 << 20
     WORD = 0x7FC1D1E5            # a quiet NaN as fp32, and as the high word of an fp64
 
-    def __init__(self, nbytes, offset):
+    def __init__(self, nbytes, offset, align=16):
         import pyfft_amd.hip as hip
         from pyfft_amd import _native as N
-        assert offset % 16 == 0 and 0 <= offset < 4096, offset
+        assert align in (4, 8, 16) and offset % align == 0 and 0 <= offset < 4096, (offset, align)
         self._N = N
         self.nbytes = int(nbytes)
         self.offset = int(offset)
@@ -608,3 +609,108 @@ def run_contract(plan, c, oop_differs, record_property):
         record_property(name + "_l1_ratio", "%.4g" % rep["l1_ratio"])
         record_property(name + "_max_ratio", "%.4g" % rep["max_ratio"])
     return reps
+
+
+# ---- the contract for forms whose sides differ (tests/test_form_instances_gpu.py) -----------------------------------------------------
+def _h2d(ptr, host):
+    from pyfft_amd import _native as N
+    host = numpy.ascontiguousarray(host)
+    N.check(N.lib.mifft_memcpy_h2d(ptr, host.ctypes.data, host.nbytes, None), "mifft_memcpy_h2d")
+
+
+def _d2h_bytes(ptr, nbytes):
+    from pyfft_amd import _native as N
+    host = numpy.empty(int(nbytes), numpy.uint8)
+    N.check(N.lib.mifft_memcpy_d2h(host.ctypes.data, ptr, host.nbytes, None), "mifft_memcpy_d2h")
+    return host
+
+
+class SidedCase(object):
+    """run_contract's sibling for the forms whose two sides differ in size and type (real <-> half spectrum; complex32 on fp16 storage)
+    or that read a third buffer (a convolution's spectrum).  Items lie along axis 0 of the host arrays; the device buffers are guarded
+    (GuardedBuffer), one per (role, size, base offset), kept for the case.  A subclass says how the plan executes
+    (execute(plan, in_ptr, out_ptr or None for in place, inverse, **kw)) and how many bytes an output takes (out_bytes(inverse))."""
+
+    def __init__(self, hip, shape, batch, index):
+        from pyfft_amd import _native as N
+        self.hip, self.N = hip, N
+        self.shape, self.batch, self.index = tuple(shape), int(batch), int(index)
+        self.n = int(numpy.prod(self.shape))
+        self.off_in, self.off_out, self.off_spec = (OFFSETS[(self.index + k) % len(OFFSETS)] for k in range(3))
+        self._bufs = {}
+
+    def close(self):
+        for b in self._bufs.values():
+            b.free()
+        self._bufs = {}
+
+    def buf(self, role, nbytes, off):
+        key = (role, int(nbytes), int(off))
+        if key not in self._bufs:
+            self._bufs[key] = GuardedBuffer(nbytes, off, align=min(16, off & -off))
+        return self._bufs[key]
+
+    def sync(self):
+        self.N.check(self.N.lib.mifft_device_sync(), "mifft_device_sync")
+
+    def run(self, plan, inverse, x, off_in=None, off_out=None, inplace=False, spec=None, refused=False, what="", **kw):
+        """One execute of the host input x between guard bands: the input at off_in bytes past its front guard, the output at off_out
+        pre-filled with all-ones bytes (a NaN in every float format), in place on the input's buffer; spec = (host array, offset): a
+        third, read-only buffer passed as spectrum=.  Afterwards every guard is intact and the input (out of place) and the spectrum
+        are bit-identical to what was uploaded.  Returns the output's bytes.  refused: the execute must raise ValueError, and the
+        output must still hold its pre-filled bytes."""
+        N = self.N
+        off_in = self.off_in if off_in is None else off_in
+        off_out = self.off_out if off_out is None else off_out
+        xb = numpy.ascontiguousarray(x).view(numpy.uint8).reshape(-1)
+        nout = self.out_bytes(inverse)
+        assert not inplace or nout == xb.size
+        a = self.buf("in", xb.size, off_in)
+        b = a if inplace else self.buf("out", nout, off_out)
+        bufs = [("input", a)] if inplace else [("input", a), ("output", b)]
+        extra = []
+        if spec is not None:
+            sb = numpy.ascontiguousarray(spec[0]).view(numpy.uint8).reshape(-1)
+            g = self.buf("spectrum", sb.size, spec[1])
+            _h2d(g.ptr, sb)
+            bufs.append(("spectrum", g))
+            extra.append((g, sb))
+            kw["spectrum"] = g.ptr
+        _h2d(a.ptr, xb)
+        if not inplace:
+            N.check(N.lib.mifft_memset(b.ptr, 0xFF, nout, None), "mifft_memset")
+        self.sync()
+        if refused:
+            try:
+                self.execute(plan, a.ptr, None if inplace else b.ptr, inverse, **kw)
+            except ValueError:
+                pass
+            else:
+                raise AssertionError("%s: accepted, a ValueError was expected" % what)
+        else:
+            self.execute(plan, a.ptr, None if inplace else b.ptr, inverse, **kw)
+        self.sync()
+        for name, g in bufs:
+            g.check_guards("%s, %s" % (what, name))
+        if not inplace:
+            assert numpy.array_equal(_d2h_bytes(a.ptr, xb.size), xb), "%s: an out-of-place execute touched its input" % what
+        for g, sb in extra:
+            assert numpy.array_equal(_d2h_bytes(g.ptr, sb.size), sb), "%s: the spectrum was written" % what
+        out = _d2h_bytes(b.ptr, nout)
+        if refused:
+            assert (out == 0xFF).all(), "%s: a refused execute changed the output" % what
+        return out
+
+    def changed(self, got, ref, skip=()):
+        """the items (equal byte ranges along the buffers) of got that differ from ref, those of `skip` left out"""
+        g, r = got.reshape(self.batch, -1), ref.reshape(self.batch, -1)
+        return [j for j in range(self.batch) if j not in skip and not numpy.array_equal(g[j], r[j])]
+
+    @staticmethod
+    def poisoned(x, layout):
+        """a copy of the host batch x with every item of `layout` (_poison_layouts) all its value: both parts of a complex number,
+        the fp16 value in complex32 data held as float16 pairs"""
+        y = numpy.array(x, copy=True)
+        for j, (_, value) in layout.items():
+            y[j] = complex(value, value) if y.dtype.kind == "c" else value
+        return y

@@ -26,7 +26,7 @@ from helpers import FakeContext
 
 GPU_MODULES = ["test_errors_gpu", "test_full_size_gpu", "test_functionality_gpu", "test_random_sweep_gpu", "test_rows_gpu",
                "test_strided_gpu", "test_persistent_gpu", "test_pairs_gpu", "test_nd_gpu", "test_generic_gpu", "test_interop_gpu",
-               "test_instances_gpu", "test_extension_instances_gpu"]
+               "test_instances_gpu", "test_extension_instances_gpu", "test_form_instances_gpu"]
 
 C64, C128, F32, F64 = numpy.complex64, numpy.complex128, numpy.float32, numpy.float64
 ALL_DTYPES = [C64, F32, C128, F64]
@@ -489,6 +489,9 @@ REGISTRY = {
     "test_extension_instances_gpu": {
         "test_extension_instance": None,     # (extension keys: extension_covered_keys)
     },
+    "test_form_instances_gpu": {
+        "test_form_instance": None,          # (form keys: form_covered_keys)
+    },
 }
 
 
@@ -783,5 +786,186 @@ def extension_covered_keys():
     for p in params_of(mod.test_extension_instance):
         shape, dtname, batch, parent, form, keys = p["case"]
         for k in extension_keys(shape, numpy.dtype(dtname), parent):
+            out.setdefault(k, p["case"])
+    return out
+
+
+# ---- the four forms (pyfft_amd/real.py, conv.py, r2r.py, half.py) -------------------------------------------------------------------
+# Plan(real=True), Plan(convolve=True), Plan(r2r=...) and Plan(dtype="complex32") run kernels of their own around (or instead of) an
+# inner power-of-two plan, whose instances universe() holds already.  The form a plan takes is the plan's own selection, made in its
+# __init__ on the model of the full part (a plan on FakeContext whose _build is skipped: no tables, no inner plans); the launch
+# geometry comes from the library's host queries and the launchers' own rules.  Keys of an execute on 16-byte-aligned bases, both
+# directions:
+#   real_row      (prec, n, direction)                       the one-launch real row (mifft_real_row_supported)
+#   real_post     (prec, direction, lanes, rank)             the separation / packing launch of composed real plans (lanes: real_post_lanes)
+#   conv_row      (prec, real, n)                            the one-launch convolution row (mifft_conv_row_supported)
+#   mul_spectrum  (prec, vector | scalar, shared | per_item, correlate)   the spectrum product of composed convolutions (vector: the
+#                                                            fp32 16-byte path of csrc/fft_aux.hip: an even point count on 16-byte bases)
+#   r2r_row       (prec, n, kind, direction)                 the one-launch cosine / sine row (mifft_r2r_row_supported)
+#   r2r_perm      (prec, rank, vec | scalar, direction)      the permutation step of the composed r2r form (launch_perm: vec = nl % 4 == 0)
+#   r2r_orbit     (prec, rank, fold | no_fold | one_lane, direction)   its twiddle step (launch_orbit: fold = L / 2 >= 64; nl = 2: one lane)
+#   r2r_fallback  (prec, n)                                  a fused r2r row run on a base that is not 16-byte aligned: the composed form
+#   half          (kernel, variant)                          the complex32 instance, half_kernel(dims, plan.variant(batch))
+FORMS = ("real", "conv", "r2r", "half")
+FORM_DTYPES = {"real": ("float32", "float64"), "conv": ("complex64", "float32", "complex128", "float64"), "r2r": ("float32", "float64"),
+               "half": ("complex32",)}
+FORM_ITEM_BYTES = {"float32": 4, "float64": 8, "complex64": 8, "complex128": 16, "complex32": 4}     # per point of the input
+R2R_KINDS = ("dct", "dst")
+_form_plans = {}
+
+
+def form_plan(form, shape, dtname, kind=None):
+    """the plan of a form on FakeContext(full_machine()), its _build skipped (the form is selected in __init__), cached; ValueError for a
+    shape the form has no plan of"""
+    key = (form, tuple(shape), dtname, kind)
+    if key not in _form_plans:
+        ctx = FakeContext(full_machine())
+        shape = tuple(int(v) for v in shape)
+        if form == "real":
+            from pyfft_amd.real import RealFFTPlan as cls
+            kw = {"dtype": dtname}
+        elif form == "conv":
+            from pyfft_amd.conv import ConvPlan as cls
+            kw = {"dtype": dtname, "real": dtname.startswith("float")}
+        elif form == "r2r":
+            from pyfft_amd.r2r import R2RPlan as cls
+            kw = {"dtype": dtname, "r2r": kind}
+        else:
+            from pyfft_amd.half import HalfFFTPlan as cls
+            kw = {"dtype": "complex32"}
+        saved = cls._build
+        cls._build = lambda self: None
+        try:
+            _form_plans[key] = cls(ctx, shape, **kw)
+        finally:
+            cls._build = saved
+    return _form_plans[key]
+
+
+def real_post_lanes(nx):
+    """threads per row segment of mifft_real_post_launch (csrc/fft_real.hip): the power of two >= nx / 2, at most 256"""
+    lanes = 1
+    while lanes < nx // 2 and lanes < 256:
+        lanes *= 2
+    return lanes
+
+
+def form_keys_of_plan(form, plan, dtname, batch, kind=None):
+    """the form keys an execute of `batch` items takes in both directions on 16-byte-aligned bases (a model plan of form_plan, or a
+    device plan: what its own selection takes); a convolution: its four spectrum variants"""
+    prec = "f64" if dtname in ("float64", "complex128") else "f32"
+    dirs = ("forward", "inverse")
+    keys = set()
+    if form == "real":
+        nx = plan._shape[-1]
+        if plan._real_form == "fused_row":
+            keys |= set(("real_row", prec, nx, d) for d in dirs)
+        else:
+            keys |= set(("real_post", prec, d, real_post_lanes(nx), len(plan._shape)) for d in dirs)
+    elif form == "conv":
+        if plan.conv_form == "fused_row":
+            keys.add(("conv_row", prec, bool(plan._real), int(plan._shape[0])))
+        else:
+            vec = prec == "f32" and plan._spec_points % 2 == 0          # (the per-item pitch is the point count: even with it)
+            for spectrum in ("shared", "per_item"):
+                for correlate in (False, True):
+                    keys.add(("mul_spectrum", prec, "vector" if vec else "scalar", spectrum, correlate))
+    elif form == "r2r":
+        kept = plan._kept
+        if plan.r2r_form == "fused_row":
+            keys |= set(("r2r_row", prec, kept[0], kind, d) for d in dirs)
+            keys.add(("r2r_fallback", prec, kept[0]))
+        elif kept:
+            nl = kept[-1]
+            perm = "vec" if nl % 4 == 0 else "scalar"
+            orbit = "one_lane" if nl == 2 else ("fold" if nl // 4 >= 64 else "no_fold")
+            for d in dirs:
+                keys.add(("r2r_perm", prec, len(kept), perm, d))
+                keys.add(("r2r_orbit", prec, len(kept), orbit, d))
+    else:
+        from pyfft_amd.half import half_kernel
+        v = plan.variant(batch)
+        keys.add(("half", half_kernel(plan.dims, v), v))
+    return keys
+
+
+def form_keys(form, shape, dtname, batch, kind=None):
+    return form_keys_of_plan(form, form_plan(form, shape, dtname, kind), dtname, batch, kind)
+
+
+def form_batch(shape):
+    """items of a form case: 67 for items of up to 2048 points (a prime above every row count of a work-group of such rows except the
+    shortest, whose one work-group 67 rows leave partly filled), else 3 (a prime above the one or two rows a work-group of longer rows
+    holds)"""
+    return 67 if _prod(shape) <= 2048 else 3
+
+
+_form_table = []
+
+
+def _form_candidate_keys():
+    """[(order, form, shape, dtype name, kind, bytes per item, batch, keys, big)] of every plan of the four forms over the power-of-two
+    shapes of up to 2^24 points; `big`: keys only a batch of universe()'s sides per side reaches (complex32's variant rule)"""
+    if not _form_table:
+        order = 0
+        for shape in _shapes(MAX_LOG2_POINTS):
+            for form in FORMS:
+                for dtname in FORM_DTYPES[form]:
+                    for kind in (R2R_KINDS if form == "r2r" else (None,)):
+                        try:
+                            plan = form_plan(form, shape, dtname, kind)
+                        except ValueError:
+                            continue            # (complex32: a shape without a one-launch kernel)
+                        item = _prod(shape) * FORM_ITEM_BYTES[dtname]
+                        batch = form_batch(shape)
+                        keys = form_keys_of_plan(form, plan, dtname, batch, kind)
+                        big = set()
+                        if form == "half":
+                            for side in UNIVERSE_SIDES:
+                                big |= form_keys_of_plan(form, plan, dtname, max(1, side // item), kind)
+                        _form_table.append((order, form, shape, dtname, kind, item, batch, keys, big - keys))
+                        order += 1
+    return _form_table
+
+
+def form_universe():
+    """{key: the first candidate (form, shape, dtype name, kind) that reaches it}"""
+    out = {}
+    for order, form, shape, dtname, kind, item, batch, keys, big in _form_candidate_keys():
+        for k in keys | big:
+            out.setdefault(k, (form, shape, dtname, kind))
+    return out
+
+
+def form_audit_cases():
+    """[(form, shape, dtype name, batch, kind, keys)]: for every key of form_universe(), the smallest candidate that reaches it at its
+    batch (bytes per side, then the candidate order); a candidate that is the smallest for several keys appears once.  A key that only
+    a bigger batch reaches raises (the audit must not silently lose an instance)."""
+    best = {}
+    for order, form, shape, dtname, kind, item, batch, keys, big in _form_candidate_keys():
+        for k in keys:
+            if k not in best or (item * batch, order) < best[k][:2]:
+                best[k] = (item * batch, order)
+    missing = sorted(set(form_universe()) - set(best), key=str)
+    if missing:
+        raise AssertionError("tests/kernel_coverage.py form_audit_cases: no case at a ragged batch reaches %r" % (missing[:40],))
+    table = dict((c[0], c) for c in _form_candidate_keys())
+    cases = {}
+    for k, (_, order) in best.items():
+        cases.setdefault(order, []).append(k)
+    out = []
+    for order in sorted(cases):
+        _, form, shape, dtname, kind, item, batch, keys, big = table[order]
+        out.append((form, shape, dtname, batch, kind, tuple(sorted(cases[order], key=str))))
+    return out
+
+
+def form_covered_keys():
+    """{key: case} over the cases of tests/test_form_instances_gpu.py, read off its parametrize mark"""
+    mod = importlib.import_module("test_form_instances_gpu")
+    out = {}
+    for p in params_of(mod.test_form_instance):
+        form, shape, dtname, batch, kind, keys = p["case"]
+        for k in form_keys(form, shape, dtname, batch, kind):
             out.setdefault(k, p["case"])
     return out

@@ -84,6 +84,45 @@ def test_every_extension_kernel_instance_has_a_contract_case():
     assert not missing, "extension kernel instances without a contract case: %r" % (missing[:40],)
 
 
+def test_every_form_kernel_instance_has_a_contract_case():
+    """The kernels of Plan(real=True), Plan(convolve=True), Plan(r2r=...) and Plan(dtype="complex32") (kernel_coverage.form_universe():
+    the one-launch rows, the real separation / packing launch, the spectrum product, the r2r steps and fallback, every complex32
+    instance) each run in tests/test_form_instances_gpu.py."""
+    import conv_cases
+    import dct_cases
+    uni = KC.form_universe()
+    kinds = {}
+    for k in uni:
+        kinds[k[0]] = kinds.get(k[0], 0) + 1
+    assert kinds["real_row"] == 2 * 29 and kinds["conv_row"] == len(conv_cases.FUSED) and kinds["r2r_row"] == 4 * len(dct_cases.FUSED)
+    assert kinds["r2r_fallback"] == len(dct_cases.FUSED) and kinds["mul_spectrum"] == 12
+    # floors for the step families: a planner change that drops a branch must not make the rule vacuous
+    assert kinds["real_post"] >= 80 and kinds["r2r_perm"] >= 24 and kinds["r2r_orbit"] >= 34 and kinds["half"] >= 200
+    prec = {numpy.float32: "f32", numpy.float64: "f64", numpy.complex64: "f32", numpy.complex128: "f64"}
+    assert set(k for k in uni if k[0] == "conv_row") == set(("conv_row", prec[dt], real, n) for dt, real, n in conv_cases.FUSED)
+    for p in ("f32", "f64"):
+        for d in ("forward", "inverse"):
+            for rank in (2, 3):
+                for e in range(9):
+                    assert ("real_post", p, d, 1 << e, rank) in uni, (p, d, 1 << e, rank)
+            for rank in (1, 2, 3):
+                assert ("r2r_orbit", p, rank, "fold", d) in uni and ("r2r_orbit", p, rank, "one_lane", d) in uni
+                assert ("r2r_perm", p, rank, "vec", d) in uni and ("r2r_perm", p, rank, "scalar", d) in uni
+        for s in ("shared", "per_item"):
+            for c in (False, True):
+                assert ("mul_spectrum", p, "scalar", s, c) in uni
+    cov = KC.form_covered_keys()
+    missing = sorted(set(uni) - set(cov), key=str)
+    assert not missing, "form kernel instances without a contract case: %r" % (missing[:40],)
+
+
+def test_form_cases_take_ragged_batches():
+    for form, shape, dtname, batch, kind, keys in KC.form_audit_cases():
+        n = int(numpy.prod(shape))
+        assert batch == (67 if n <= 2048 else 3), (form, shape, batch)
+        assert set(keys) <= KC.form_keys(form, shape, dtname, batch, kind)
+
+
 def test_extension_cases_take_their_forms_and_ragged_batches():
     top32, beyond32 = KC.long_limits(numpy.complex64)
     top64, beyond64 = KC.long_limits(numpy.complex128)
