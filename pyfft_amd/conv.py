@@ -127,10 +127,21 @@ class ConvPlan(object):
             return
         if need and self._context.capturing():
             raise RuntimeError("pyfft_amd: execute() on a capturing stream needs one eager execute() of the same batch first")
-        if self._captured and self._scratch is not None:
-            self._capture_keepalive.append(self._scratch)
-        self._last_batch = batch
-        self._scratch = self._context.allocate(batch * self._spec_points * self._cdtype.itemsize) if need else None
+        self._release_scratch()
+        if need:
+            self._scratch = self._context.allocate(batch * self._spec_points * self._cdtype.itemsize)
+        self._last_batch = batch         # (committed only now: after a failed allocation the plan is as close() leaves it)
+
+    def _release_scratch(self):
+        """Let go of the scratch: to the keep-alive list once a graph has recorded an execute (it replays on it); else, where it came
+        from a mempool, only after the plan's own asynchronous executes have finished with it (hipFree does that waiting itself)."""
+        if self._scratch is not None:
+            if self._captured:
+                self._capture_keepalive.append(self._scratch)
+            else:
+                self._context.wait_scratch()
+        self._scratch = None
+        self._last_batch = 0
 
     def _check_buffers(self, batch, x, y, spectrum, spectrum_batch):
         data_bytes = batch * self._size * self._dtype.itemsize
@@ -258,10 +269,7 @@ class ConvPlan(object):
         try:
             self.finish()
         finally:
-            if self._captured and self._scratch is not None:
-                self._capture_keepalive.append(self._scratch)
-            self._scratch = None
-            self._last_batch = 0
+            self._release_scratch()
             self._inner.close()
 
     def release_captured(self):

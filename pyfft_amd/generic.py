@@ -142,6 +142,9 @@ class _SubContext(object):
     def wait(self):
         self._ctx.wait()
 
+    def wait_scratch(self):
+        self._ctx.wait_scratch()
+
     def flush(self):
         pass
 
@@ -364,20 +367,40 @@ class GenericFFTPlan(object):
         self._context.flush()
         return self._context.getQueue()
 
-    def _prepare(self, batch):
-        if batch == self._last_batch:
+    def _prepare(self, batch, capturing=False, long_scratch=False):
+        """Work arrays of the batch (long_scratch: the scratch of a long smooth transform run in place, allocated by the first
+        execute that needs it).  `capturing`: the stream of this call records into a graph, where nothing can be allocated or
+        released.  The new state is committed only after every allocation has succeeded; after a failure the plan is as close()
+        leaves it."""
+        needs = self._uses_work or (long_scratch and self._direct_long is not None)
+        if batch == self._last_batch and (self._work is not None or not needs):
             return
-        if self._captured and (self._work is not None or self._rows is not None):
-            self._capture_keepalive.append((self._work, self._rows))      # (a recorded graph replays on them: hip.Graph docstring)
+        if capturing and needs:
+            raise RuntimeError("pyfft_amd: execute() on a capturing stream needs one eager execute() of the same batch first")
+        self._release_work(capturing)
+        if needs:
+            isz = self._cdtype.itemsize
+            nt = batch * self._ntiles
+            work = self._context.allocate(nt * self._size * isz)
+            rows = None
+            if self._uses_work:
+                worst = max((self._size // ax.n) * ax.m for ax in self._axes)
+                rows = self._context.allocate(nt * worst * isz)
+            self._work, self._rows = work, rows
         self._last_batch = batch
-        if not self._uses_work:
-            self._work = None           # no work arrays (a long smooth transform in place allocates its scratch on demand)
-            return
-        isz = self._cdtype.itemsize
-        nt = batch * self._ntiles
-        self._work = self._context.allocate(nt * self._size * isz)
-        worst = max((self._size // ax.n) * ax.m for ax in self._axes)
-        self._rows = self._context.allocate(nt * worst * isz)
+
+    def _release_work(self, capturing=False):
+        """Let go of the work arrays: to the keep-alive list once a graph has recorded an execute (it replays on them: hip.Graph
+        docstring) or while one is recording (a capture must not see a release); else, where they came from a mempool, only after
+        the plan's own asynchronous executes have finished with them."""
+        if self._work is not None or self._rows is not None:
+            if self._captured or capturing:
+                self._capture_keepalive.append((self._work, self._rows))
+            else:
+                self._context.wait_scratch()
+        self._work = None
+        self._rows = None
+        self._last_batch = 0
 
     @on_plan_device
     def _execute(self, wait_for_finish, inverse, batch, ins, outs):
@@ -386,13 +409,14 @@ class GenericFFTPlan(object):
         if batch < 1:
             raise ValueError("batch must be positive")
         self.check()
-        self._prepare(batch)
         ptr = ctx.pointer_of
         ctx.createQueue(ins + outs)
-        ctx.order_scratch()
-        if ctx.capturing():
-            # recorded into a graph (work arrays must exist: one eager execute of the batch first): the graph keeps this plan alive,
-            # the plan keeps the work arrays of the recorded batch
+        capturing = ctx.capturing()          # (of the stream of THIS call: createQueue has just chosen it)
+        self._prepare(batch, capturing, long_scratch=self._direct_long is not None and ptr(ins[0]) == ptr(outs[0]))
+        ctx.order_scratch(capturing)
+        if capturing:
+            # recorded into a graph (_prepare has refused a batch without work arrays): the graph keeps this plan alive, the plan
+            # keeps the work arrays of the recorded batch
             from .hip import Graph
             self._captured = True
             Graph.retain(self)
@@ -438,9 +462,7 @@ class GenericFFTPlan(object):
             factor = self._scale if not inv else 1.0 / ((n if self._normalize else 1.0) * self._scale)
             src, dst = ptr(ins[0]), ptr(outs[0])
             mid = dst
-            if src == dst:                  # in place: the transposing first pass needs somewhere else to write
-                if self._work is None:
-                    self._work = ctx.allocate(batch * n * self._cdtype.itemsize)
+            if src == dst:                  # in place: the transposing first pass needs somewhere else to write (_prepare)
                 mid = ptr(self._work)
             N.check(N.lib.mifft_launch_mixed_long(self._precision, n1, n2, batch, src, mid, dst, tw1, tw2, lo, hi, shift,
                                                   1 if inv else 0, factor, ctx.stream_handle()), "mifft_launch_mixed_long")
@@ -565,6 +587,23 @@ class GenericFFTPlan(object):
         """Non-blocking: raise if a completed asynchronous execute() of an inner plan reported invalid results."""
         for p in self._inner_plans():
             p.check()
+
+    def close(self):
+        """Wait for outstanding work and release the work arrays now; the plan stays usable.  What a recorded graph replays on is
+        kept until release_captured() (FFTPlan.close)."""
+        try:
+            self.finish()
+        finally:
+            self._release_work()
+            for p in self._inner_plans():
+                p.close()
+
+    def release_captured(self):
+        self.finish()
+        self._capture_keepalive = []
+        self._captured = False
+        for p in self._inner_plans():
+            p.release_captured()
 
     def _executeInterleaved(self, data_in, data_out=None, inverse=False, batch=1, wait_for_finish=None):
         if data_out is None:

@@ -132,6 +132,7 @@ class HalfFFTPlan(object):
         self._scale = float(scale)
         self._wait_for_finish = wait_for_finish
         self._captured = False
+        self._capture_keepalive = []     # (always empty: the plan owns no batch-sized scratch; the attribute the other plans have)
         self._tables = []
         on_plan_device(HalfFFTPlan._build)(self)
 

@@ -563,6 +563,14 @@ class Context(object):
     def wait(self):
         N.check(N.lib.mifft_stream_sync(self.stream_handle()), "mifft_stream_sync")
 
+    def wait_scratch(self):
+        """Called before a plan lets go of scratch its own asynchronous executes may still use.  Without a mempool nothing is to do:
+        hipFree waits for the device.  A mempool may hand the block to its next caller at once, on any stream, so the stream the
+        plan enqueued on last (order_scratch) is waited for first.  Never called for scratch a graph recorded: that is kept alive."""
+        if self._mempool is None or self._last_stream_handle is None:
+            return
+        N.check(N.lib.mifft_stream_sync(self._last_stream_handle[0]), "mifft_stream_sync")
+
     def flush(self):
         pass
 
@@ -586,7 +594,9 @@ def Plan(*args, **kwds):
     an object with a `.device` index) or None = the current device.  HIP has one primary context per device; a plan
     built for a device that is not the caller's current one makes it current around its own calls and restores the
     caller's afterwards, so one process can hold a plan per GPU (buffers must live on the plan's device).
-    `mempool`: any object with an allocate(nbytes) method returning a buffer-like object.
+    `mempool`: any object with an allocate(nbytes) method returning a buffer-like object.  A plan waits for the stream it enqueued
+    on last before it drops scratch that came from the pool (a batch change, close()), so a recycling pool never gets a block back
+    that an asynchronous execute of the plan still uses.
     `real=True`: real-input transforms (pyfft_amd/real.py): `dtype` float32 / float64 (or complex64 / complex128) names the precision,
     execute(real_in, spectrum_out) / execute(spectrum_in, real_out, inverse=True), out of place, numpy's rfftn / irfftn layout.
     `dtype="complex32"` (or torch.complex32): half-precision transforms (pyfft_amd/half.py): interleaved fp16 data, fp32 arithmetic, one

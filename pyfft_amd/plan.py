@@ -426,23 +426,32 @@ class FFTPlan(object):
 
     PERSISTENT = ("fused2", "fusedp", "fused2z")
 
-    def _prepare(self, batch):
+    def _prepare(self, batch, capturing=False):
         """Choose the strategy when the batch changes (plan.py:179-192); the plan-owned scratch of that strategy is allocated by the
-        first execute that needs it (_ensure_scratch): an out-of-place execute that takes the one-launch route (_runs_oop_nd) needs none."""
+        first execute that needs it (_ensure_scratch): an out-of-place execute that takes the one-launch route (_runs_oop_nd) needs none.
+        `capturing`: the stream of this call records into a graph, which must not see a release."""
         if self._last_batch_size == batch:
             return
-        self._retain_captured_scratch()
+        self._release_temp(capturing)
         self._last_batch_size = batch
         self._last_call_key = None
         self._strategy = self._select_strategy(batch)
-        self._tempmemobj = None
         self._scratch_ready = False
 
-    def _retain_captured_scratch(self):
+    def _release_temp(self, capturing=False):
+        """Let go of the temp buffer / ring of the previous batch.  Recorded into a graph (or about to be let go of inside a capture):
+        it moves to the keep-alive list.  From a mempool: the plan's own asynchronous executes may still run on it, and a recycling
+        pool hands it to its next caller at once, so the plan waits for its stream first (hipFree does that waiting itself)."""
+        self._retain_captured_scratch(capturing)
+        if self._tempmemobj is not None and not (self._captured or capturing):
+            self._context.wait_scratch()
+        self._tempmemobj = None
+
+    def _retain_captured_scratch(self, capturing=False):
         """A captured launch holds raw device addresses of this plan's scratch (ring / temp buffer, counter sets, pinned error word,
         side streams): once an execute() has been recorded into a graph, scratch that is about to be replaced or released moves to
         a keep-alive list instead of being freed, so that later replays of that graph still find it (hip.Graph docstring)."""
-        if self._captured:
+        if self._captured or capturing:
             held = (self._tempmemobj, self._counters, self._errword, self._side_streams, self._side_events)
             if any(h is not None for h in held) and not any(k is held or k == held for k in self._capture_keepalive):
                 self._capture_keepalive.append(held)
@@ -456,17 +465,33 @@ class FFTPlan(object):
         if self._scratch_ready:
             return
         ctx = self._context
-        p = self._params
         batch = self._last_batch_size
         if self._scratch_needed() and ctx.capturing():
             # scratch, counters and side streams are allocated here, which a capturing stream cannot record
             raise RuntimeError("pyfft_amd: execute() on a capturing stream needs one eager execute() of the same batch (and the same "
                                "in-place / out-of-place form) first")
-        self._scratch_ready = True
+        try:
+            self._allocate_scratch(batch)
+        except BaseException:
+            # nothing batch-sized of a step that failed half way is kept: no temp buffer / ring, no counter sets, batch 0, as close()
+            # leaves them, so the next execute of any batch allocates all of it again, at its own size (what a recorded graph replays
+            # on went to the keep-alive list when the batch changed: _prepare).  The side streams, their events and the pinned error
+            # word are not sized by the batch and stay: work in flight may still use them, and only close() waits for it first
+            self._tempmemobj = None
+            self._counters = None
+            self._last_batch_size = 0
+            self._last_call_key = None
+            raise
+        self._scratch_ready = True       # (only now: every allocation of the step has succeeded)
+
+    def _allocate_scratch(self, batch):
+        ctx = self._context
+        p = self._params
         if self._strategy[0] == "pipelined" and self._side_streams is None:
             from .hip import Stream, Event
-            self._side_streams = [Stream() for _ in range(self._strategy[2])]
-            self._side_events = [Event() for _ in range(self._strategy[2] + 1)]
+            streams = [Stream() for _ in range(self._strategy[2])]
+            events = [Event() for _ in range(self._strategy[2] + 1)]
+            self._side_streams, self._side_events = streams, events
         if not self._temp_buffer_needed and self._strategy[0] not in self.PERSISTENT:
             return
         if self._strategy[0] in self.PERSISTENT:
@@ -474,9 +499,8 @@ class FFTPlan(object):
             # two counter sets: every launch runs on one and zeroes the other (mifft_fused_sync), so no memset precedes a launch;
             # a third one for launches captured into a graph (_fused_sync)
             planes = int(p.z) if self._strategy[0] == "fused2z" else 1
-            self._counter_bytes = N.fused2_counter_bytes(batch * planes)
-            self._counters = ctx.allocate_raw(3 * self._counter_bytes)
-            self._counters_clean = False
+            counter_bytes = N.fused2_counter_bytes(batch * planes)
+            counters = ctx.allocate_raw(3 * counter_bytes)
             if self._errword is None:
                 from .hip import ErrorWord
                 self._errword = ErrorWord()
@@ -488,6 +512,10 @@ class FFTPlan(object):
         # plan.py:189-190; same total size)
         item = p.size // int(p.z) if self._strategy[0] == "fused2z" else p.size      # fused2z: the ring holds (y, x) planes
         self._tempmemobj = ctx.allocate(item * items * p.complex_nbytes)
+        if self._strategy[0] in self.PERSISTENT:
+            self._counter_bytes = counter_bytes
+            self._counters = counters
+            self._counters_clean = False
 
     def _fused_sync(self, stream, capturing=False):
         """mifft_fused_sync of the coming persistent launch: the counter set it runs on (zero: the previous launch cleared it, or
@@ -650,7 +678,7 @@ class FFTPlan(object):
             raise RuntimeError("pyfft_amd: execute() on a capturing stream cannot wait for the result: build the plan with stream= "
                                "(or wait_for_finish=False), or pass wait_for_finish=False to this call")
         if self._last_batch_size != batch:
-            self._prepare(batch)
+            self._prepare(batch, capturing)
         # small transforms are launch-bound (a 32 MiB execute is ~12 us of device time): the pointer triples of the last
         # call are kept, so that repeated executes on the same buffers skip rebuilding them
         ptr = ctx.pointer_of
@@ -715,9 +743,8 @@ class FFTPlan(object):
         try:
             self.finish()
         finally:
-            self._retain_captured_scratch()      # (a plan that was captured into a graph keeps what the graph replays on)
+            self._release_temp()                 # (a plan that was captured into a graph keeps what the graph replays on)
             self._scratch_ready = False
-            self._tempmemobj = None
             self._counters = None
             self._side_streams = None
             self._side_events = None

@@ -129,10 +129,21 @@ class RealFFTPlan(object):
             return
         if self._inner is not None and batch != self._last_batch and self._context.capturing():
             raise RuntimeError("pyfft_amd: execute() on a capturing stream needs one eager execute() of the same batch first")
-        if self._captured and self._scratch is not None:
-            self._capture_keepalive.append(self._scratch)
-        self._last_batch = batch
-        self._scratch = self._context.allocate(batch * self._packed_points * self._cdtype.itemsize) if self._inner is not None else None
+        self._release_scratch()
+        if self._inner is not None:
+            self._scratch = self._context.allocate(batch * self._packed_points * self._cdtype.itemsize)
+        self._last_batch = batch         # (committed only now: after a failed allocation the plan is as close() leaves it)
+
+    def _release_scratch(self):
+        """Let go of the scratch: to the keep-alive list once a graph has recorded an execute (it replays on it); else, where it came
+        from a mempool, only after the plan's own asynchronous executes have finished with it (hipFree does that waiting itself)."""
+        if self._scratch is not None:
+            if self._captured:
+                self._capture_keepalive.append(self._scratch)
+            else:
+                self._context.wait_scratch()
+        self._scratch = None
+        self._last_batch = 0
 
     def _post(self, inverse, batch, src, dst, scale):
         d = N.MifftRealPost()
@@ -251,10 +262,7 @@ class RealFFTPlan(object):
         try:
             self.finish()
         finally:
-            if self._captured and self._scratch is not None:
-                self._capture_keepalive.append(self._scratch)
-            self._scratch = None
-            self._last_batch = 0
+            self._release_scratch()
             if self._inner is not None:
                 self._inner.close()
 

@@ -162,6 +162,61 @@ class FakeContext(object):
         return False
 
 
+class FailingPool(object):
+    """A pool for plans on PooledFakeContext (tests/test_lifecycle_cpu.py): every allocate(nbytes) is logged in `requests`, the
+    fail_at-th call (counted from 1 since the last arm()) raises MemoryError.  Blocks are objects, so a test sees which one a plan holds."""
+
+    class Block(object):
+        def __init__(self, nbytes):
+            self.nbytes = int(nbytes)
+
+    def __init__(self):
+        self.arm(None)
+
+    def arm(self, fail_at):
+        self.fail_at = fail_at
+        self.requests = []
+
+    def allocate(self, nbytes):
+        self.requests.append(int(nbytes))
+        if self.fail_at is not None and len(self.requests) == self.fail_at:
+            raise MemoryError("FailingPool: allocation %d (%d bytes) fails" % (self.fail_at, nbytes))
+        return FailingPool.Block(nbytes)
+
+
+class PooledFakeContext(FakeContext):
+    """FakeContext whose allocate() and allocate_raw() go through a FailingPool, with the two calls of a real context that a plan makes
+    when it lets go of scratch: wait_scratch() (counted) and capturing() (settable)."""
+
+    def __init__(self, machine, pool=None, capturing=False):
+        FakeContext.__init__(self, machine)
+        self.pool = pool if pool is not None else FailingPool()
+        self.allocate = self.allocate_raw = self.pool.allocate
+        self.is_capturing = capturing
+        self.waits = 0          # wait_scratch() calls
+        self.syncs = 0          # wait() calls (finish())
+
+    def capturing(self):
+        return self.is_capturing
+
+    def wait_scratch(self):
+        self.waits += 1
+
+    def wait(self):
+        self.syncs += 1
+
+    # what an execute() calls before its first launch; every launch takes stream_handle() as an argument, so a plan that goes on
+    # to one stops here
+    def createQueue(self, buffers=()):
+        pass
+
+    def order_scratch(self, capturing=None):
+        pass
+
+    def stream_handle(self):
+        raise AssertionError("the plan went on to a launch")
+
+
 # ---- the per-instance accuracy contract (tests/test_instances_gpu.py; docs/parity.md) ------------------------------------------------
 NOISE_PERIOD = (1 << 22) + 17          # the period of _noise: element i of a _test_data set is element i % NOISE_PERIOD of its first block
 SAMPLE_ALL_POINTS = 1 << 22            # up to this many points per side every item is checked, beyond it the first, the middle and the last
