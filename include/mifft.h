@@ -259,6 +259,20 @@ int mifft_pass_supported(int32_t kind, int32_t precision, int32_t L, int32_t var
 int mifft_launch_pass(const mifft_pass *pass, const void *in0, const void *in1, void *out0, void *out1,
                       mifft_stream_t stream);
 
+/* Which kernel form mifft_launch_pass runs for a MIFFT_PASS_ND descriptor: a pure query (it never touches a device), the one selector
+ * the launch itself goes through.  aliased: bit 0 = the call would have in0 == out0, bit 1 = in1 == out1 (planes on both sides only).
+ * The answer also depends on the calling thread's development switches.  Returns a MIFFT_ND_KERNEL_* constant, else the error code (with
+ * its message) mifft_launch_pass gives for that descriptor before it touches data: an invalid descriptor, a shape without a kernel, a
+ * shape whose kernel exists out of place only asked for in place. */
+#define MIFFT_ND_KERNEL_WAVE  1 /* wave-autonomous (16, 16) fp32 plane (fft_wave.hpp): MIFFT_DEBUG_FORCE_WAVE only */
+#define MIFFT_ND_KERNEL_ND2Z  2 /* several work-groups per transform, interleaved, out of place (fft_nd2z.hpp) */
+#define MIFFT_ND_KERNEL_ND2   3 /* fixed shape, interleaved on both sides (fft_nd2.hpp) */
+#define MIFFT_ND_KERNEL_ND2ZP 4 /* several work-groups per transform, planes on both sides, out of place (fft_nd2zp.hpp) */
+#define MIFFT_ND_KERNEL_ND2P  5 /* fixed shape, dense planes on both sides, 16-byte accesses (fft_nd2p.hpp) */
+#define MIFFT_ND_KERNEL_ND2T  6 /* fixed shape in its tiled form, planes in (fft_nd2t.hpp: planes or interleaved out) */
+#define MIFFT_ND_KERNEL_ND    7 /* run-time-shaped kernel (fft_nd.hpp), up to mifft_nd_max_points_for() points, any sides */
+int mifft_nd_kernel(const mifft_pass *pass, int32_t aliased);
+
 /*
  * Pass pairs: two CONSECUTIVE passes of a chain run by one launch on tiles that hold the points of both, so that a 3-D
  * transform whose (y, x) plane fits no work-group still crosses HBM twice instead of three times.  With the y axis

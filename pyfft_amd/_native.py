@@ -33,6 +33,7 @@ FLAG_STREAM_SRC, FLAG_STREAM_DST = 4, 8
 FLAG_WRITE_THROUGH = 32
 FLAG_PAIR_WITH_NEXT = 16
 HALF_KERNEL_TILE, HALF_KERNEL_ROW, HALF_KERNEL_ND2, HALF_KERNEL_ND = 1, 2, 3, 4    # mifft_half_kernel
+ND_KERNEL_WAVE, ND_KERNEL_ND2Z, ND_KERNEL_ND2, ND_KERNEL_ND2ZP, ND_KERNEL_ND2P, ND_KERNEL_ND2T, ND_KERNEL_ND = 1, 2, 3, 4, 5, 6, 7    # mifft_nd_kernel
 FUSED2_COUNTER_STRIDE = 64          # MIFFT_FUSED2_COUNTER_STRIDE (uint32 words between two counters)
 
 
@@ -215,6 +216,7 @@ PROTOTYPES = {
     "mifft_nd_shape_supported": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32]),
     "mifft_pass_supported": (ctypes.c_int, [_i32, _i32, _i32, _i32]),
     "mifft_launch_pass": (ctypes.c_int, [_pass_p, _vp, _vp, _vp, _vp, _vp]),
+    "mifft_nd_kernel": (ctypes.c_int, [_pass_p, _i32]),
     "mifft_pair_split": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32]),
     "mifft_pass_pair_supported": (ctypes.c_int, [_pass_p, _pass_p]),
     "mifft_pair_kernel_supported": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32, _i32]),

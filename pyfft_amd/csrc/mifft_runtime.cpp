@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
+#include <initializer_list>
 
 #include "../../include/mifft.h"
 #include "mifft_internal.h"
@@ -43,7 +44,28 @@ int hip_check(hipError_t e, const char* what) {
     return set_err((int)e, "%s: %s (%d)", what, hipGetErrorString(e), (int)e);
 }
 
+// what a kernel launcher of this library returned (0, -1 = grid too large, else a hipError_t) as the entry point's result; a launcher's
+// -2 ("no such kernel") is the caller's to name
+int launched(int rc) {
+    if (rc == -1) return set_err(MIFFT_E_INVALID, "grid too large");
+    return hip_check((hipError_t)rc, "kernel launch");
+}
+
 bool is_pow2(long long v) { return v > 0 && (v & (v - 1)) == 0; }
+bool bad_precision(int precision) { return precision != MIFFT_F32 && precision != MIFFT_F64; }
+long long complex_bytes(int precision) { return precision == MIFFT_F64 ? 16 : 8; }
+// is one of the addresses no multiple of mask + 1 (null counts as aligned)
+bool misaligned(uintptr_t mask, std::initializer_list<const void*> ptrs) {
+    uintptr_t all = 0;
+    for (const void* p : ptrs) all |= (uintptr_t)p;
+    return (all & mask) != 0;
+}
+bool misaligned_complex(int precision, std::initializer_list<const void*> ptrs) { return misaligned((uintptr_t)complex_bytes(precision) - 1, ptrs); }
+// do the byte ranges [a, a + na) and [b, b + nb) share a byte
+bool overlap(const void* a, uintptr_t na, const void* b, uintptr_t nb) { return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na; }
+// the two sides of a pass: scalar planes, or interleaved (always for MIFFT_INTERLEAVED; for MIFFT_SPLIT the plan's temp buffer)
+bool planes_in(const mifft_pass* p) { return p->layout == MIFFT_SPLIT && !(p->flags & MIFFT_FLAG_SRC_INTERLEAVED); }
+bool planes_out(const mifft_pass* p) { return p->layout == MIFFT_SPLIT && !(p->flags & MIFFT_FLAG_DST_INTERLEAVED); }
 // a * b * c (all >= 0) without overflow, or -1
 long long mul3_checked(long long a, long long b, long long c) {
     long long ab, abc;
@@ -53,11 +75,9 @@ long long mul3_checked(long long a, long long b, long long c) {
 // rows of the mixed-radix / Bluestein launchers: interleaved complex numbers, 8-byte (fp32) / 16-byte (fp64) aligned; an in-place call
 // must keep every row where it is (a work-group stores its rows while others have not loaded theirs yet)
 const char* check_rows(int precision, const void* in, const void* out, long long rows, long long n, long long stride_in, long long stride_out) {
-    const uintptr_t mask = precision == MIFFT_F64 ? 15 : 7;
-    if (((uintptr_t)in | (uintptr_t)out) & mask) return "data buffers must be aligned to one complex number";
+    if (misaligned_complex(precision, {in, out})) return "data buffers must be aligned to one complex number";
     if (in == out && stride_in != stride_out) return "an in-place call needs equal row strides on both sides";
-    const long long esz = precision == MIFFT_F64 ? 16 : 8;
-    if (mul3_checked(rows, stride_in > stride_out ? stride_in : stride_out, esz) < 0) return "rows * stride overflows";
+    if (mul3_checked(rows, stride_in > stride_out ? stride_in : stride_out, complex_bytes(precision)) < 0) return "rows * stride overflows";
     (void)n;
     return nullptr;
 }
@@ -70,25 +90,75 @@ int ilog2(long long v) {
     return r;
 }
 
+// ---- which kernel form runs an MIFFT_PASS_ND pass ---------------------------------------------------------------------------------
+// One gate per form that has instances of its own: the form's development switches, its instance query and its minimum-row-bytes rule.
+// select_nd() (what a launch runs), nd_has_kernel() (what validate() accepts) and mifft_nd_shape_supported() (what a planner is told)
+// are all written in terms of these.  MIFFT_DEBUG_NO_ND2: the run-time-shaped kernel only.
+
+// fixed shapes, interleaved on both sides (fft_nd2.hpp; the generated tables fft_nd2_<prec>_*.hip).  The instance query alone: the
+// switch acts when a pass is launched (select_nd), not on what the planner is told
+bool nd2_instance(bool f64, int x, int y, int z) { return (f64 ? mifft_nd2_f64_supported(x, y, z) : mifft_nd2_f32_supported(x, y, z)) == 0; }
+
+// several work-groups per transform, interleaved on both sides, out of place only (fft_nd2z.hpp, round 5).  It is only instantiated where
+// it measured faster, at 32 MiB and at 1 GiB per side.  level 1: a kernel exists -- what a shape without another one-launch kernel runs
+// (FOUR two-per-CU tiles; the plan only builds such a pass for its out-of-place executes), and what runs in SMALL launches (the plan marks
+// those with MIFFT_FLAG_WRITE_THROUGH: up to half the last-level cache per side); level 2: one that is preferred at every buffer size (the
+// one-tile-per-CU shapes).  A/B: MIFFT_DEBUG_ALT_ROWS = 6 never
+bool nd2z_gate(bool f64, int x, int y, int z, int level) {
+    return g_debug[MIFFT_DEBUG_NO_ND2] == 0 && g_debug[MIFFT_DEBUG_ALT_ROWS] != 6 && mifft_nd2z(f64 ? 1 : 0, x, y, z, nullptr, nullptr, level) == 0;
+}
+
+// planes on BOTH sides of a published shape, dense, 16 bytes per lane and plane (fft_nd2p.hpp, round 6); the tiled kernel below moves one
+// scalar per lane and plane through the tiling's address arithmetic (0.69-0.86 of the interleaved twin at 1 GiB).  level 1: an instance
+// exists; 2: it is also the choice for small launches.  MIFFT_DEBUG_ALT_ROWS = 7: the tiled kernel (A/B)
+bool nd2p_gate(bool f64, int x, int y, int z, int level) {
+    return g_debug[MIFFT_DEBUG_NO_ND2] == 0 && g_debug[MIFFT_DEBUG_NARROW_TILES] != 1 && g_debug[MIFFT_DEBUG_ALT_ROWS] != 7 &&
+           mifft_nd2p(f64 ? 1 : 0, x, y, z, nullptr, nullptr, level) == 0;
+}
+
+// ... and its one-tile-per-CU shapes as two half-size work-groups per transform, out of place (fft_nd2zp.hpp; levels as for nd2z_gate;
+// MIFFT_DEBUG_ALT_ROWS = 6: never several work-groups per transform, as for interleaved data)
+bool nd2zp_gate(bool f64, int x, int y, int z, int level) {
+    return g_debug[MIFFT_DEBUG_NO_ND2] == 0 && g_debug[MIFFT_DEBUG_NARROW_TILES] != 1 && g_debug[MIFFT_DEBUG_ALT_ROWS] != 7 &&
+           g_debug[MIFFT_DEBUG_ALT_ROWS] != 6 && mifft_nd2zp(f64 ? 1 : 0, x, y, z, nullptr, nullptr, level) == 0;
+}
+
+// planes on the input side (planes -> planes: a single-pass N-D plan; planes -> interleaved: the plane pass of a split-complex multi-pass
+// plan, fft_nd2t_split_in.hip): the fixed-shape stage chain exists for planes in its TILED form (fft_nd2t.hpp, second batch of round 4)
+// -- a dense batch is the tiling with one tile per "parent".  (128, 128) planes at 1 GiB: 0.471 on the run-time-shaped kernel -> 0.653
+// (interleaved fixed-shape kernel 0.700), (64, 64) 0.535 -> 0.597, fp64 16^3 0.510 -> 0.584; shapes whose x rows are shorter than 128 bytes
+// per plane stay on the run-time-shaped kernel -- fp32 (16, 16) 0.717 against 0.460, 16^3 0.674 against 0.475: their tiles move scalars over
+// short runs (profiles/r04_at_rows_split.log).  min_row_bytes: 128 to RUN it; 256 to PREFER it to two passes when planning (fp64
+// (128, 128) 0.374 as two passes -> 0.568, (16, 32, 32) 0.338 -> 0.499; fp32 32^3, 128-byte rows, measured 0.285 against 0.307 for its
+// two passes and keeps them -- same log)
+bool nd2t_gate(bool f64, int x, int y, int z, int min_row_bytes) {
+    return g_debug[MIFFT_DEBUG_NO_ND2] == 0 && g_debug[MIFFT_DEBUG_NARROW_TILES] != 1 && x * (f64 ? 8 : 4) >= min_row_bytes &&
+           mifft_nd2t_split(f64, x, y, z, nullptr, nullptr, nullptr, 1) == 0;
+}
+
+// validate(): is there a kernel for the pass's shape and sides at all.  Beyond the run-time-shaped kernel's tile: a fixed instance of the
+// sides' own (planes on the input side: the tiled kernel's planning threshold, or a dense planes instance), or one that exists out of
+// place only -- select_nd refuses an in-place call of those, with its own message
+bool nd_has_kernel(const mifft_pass* p) {
+    const bool f64 = p->precision == MIFFT_F64;
+    const int x = p->L, y = (int)p->M, z = (int)p->S;
+    const long long n = mul3_checked(p->L, p->M, p->S);
+    if (n >= 0 && n <= mifft_nd_max_points(f64)) return true;
+    if (!planes_in(p)) return !planes_out(p) && (nd2_instance(f64, x, y, z) || nd2z_gate(f64, x, y, z, 1));
+    return nd2t_gate(f64, x, y, z, 256) || nd2p_gate(f64, x, y, z, 1) || (planes_out(p) && nd2zp_gate(f64, x, y, z, 1));
+}
+
 int validate(const mifft_pass* p) {
     if (!p) return set_err(MIFFT_E_INVALID, "null pass descriptor");
     if (p->kind != MIFFT_PASS_COL && p->kind != MIFFT_PASS_ROW && p->kind != MIFFT_PASS_ND) return set_err(MIFFT_E_INVALID, "bad pass kind %d", p->kind);
-    if (p->precision != MIFFT_F32 && p->precision != MIFFT_F64) return set_err(MIFFT_E_INVALID, "bad precision %d", p->precision);
+    if (bad_precision(p->precision)) return set_err(MIFFT_E_INVALID, "bad precision %d", p->precision);
     if (p->layout != MIFFT_INTERLEAVED && p->layout != MIFFT_SPLIT) return set_err(MIFFT_E_INVALID, "bad layout %d", p->layout);
     if (!is_pow2(p->L) || (p->L < 2 && p->kind != MIFFT_PASS_ND)) return set_err(MIFFT_E_INVALID, "L=%d is not a power of two >= 2", p->L);
     if (p->outer < 0) return set_err(MIFFT_E_INVALID, "negative outer count");
     if (p->kind == MIFFT_PASS_ND) {
         if (!is_pow2(p->M) || !is_pow2(p->S)) return set_err(MIFFT_E_INVALID, "ND pass: y and z must be powers of two");
         const long long n = (long long)p->L * p->M * p->S;
-        const bool both_interleaved = p->layout != MIFFT_SPLIT || ((p->flags & MIFFT_FLAG_SRC_INTERLEAVED) && (p->flags & MIFFT_FLAG_DST_INTERLEAVED));
-        // (planes on the input side at least: the tiled fixed-shape kernel takes planes -> planes and planes -> interleaved)
-        const bool both_split = p->layout == MIFFT_SPLIT && !(p->flags & MIFFT_FLAG_SRC_INTERLEAVED);
-        // (interleaved shapes that exist out of place only: launch_nd refuses an in-place call, with its own message)
-        if (n < 4 || (mifft_nd_shape_supported(p->precision, p->L, (int32_t)p->M, (int32_t)p->S,
-                                               both_interleaved ? MIFFT_VARIANT_INTERLEAVED_ONLY : both_split ? MIFFT_VARIANT_SPLIT_ONLY : 0) != 0 &&
-                      !(both_interleaved && mifft_nd_shape_supported(p->precision, p->L, (int32_t)p->M, (int32_t)p->S, MIFFT_VARIANT_OUT_OF_PLACE_ONLY) == 0) &&
-                      !(both_split && !(p->flags & MIFFT_FLAG_DST_INTERLEAVED) &&
-                        mifft_nd_shape_supported(p->precision, p->L, (int32_t)p->M, (int32_t)p->S, MIFFT_VARIANT_SPLIT_OUT_OF_PLACE) == 0)))
+        if (n < 4 || !nd_has_kernel(p))
             return set_err(MIFFT_E_UNSUPPORTED, "ND pass: no kernel for %d x %lld x %lld (%lld points)", p->L, (long long)p->M, (long long)p->S, n);
         if ((p->L > 1 && !p->tw_L) || (p->M > 1 && !p->tw_lo) || (p->S > 1 && !p->tw_hi)) return set_err(MIFFT_E_INVALID, "ND pass: twiddle table missing");
         return 0;
@@ -108,21 +178,20 @@ int validate(const mifft_pass* p) {
     return 0;
 }
 
+// development switch MIFFT_DEBUG_STORE: overrides the store side of a TileArgs.nt / PairArgs.nt for A/B measurements
+int store_override(int nt) {
+    const int how = g_debug[MIFFT_DEBUG_STORE];
+    return how == 1 ? (nt & 1) | 2 : how == 2 ? (nt & 1) | 4 : how == 3 ? nt & 1 : nt;
+}
 // TileArgs.nt from the MIFFT_FLAG_STREAM_* hints: bit 0 non-temporal loads, bit 1 non-temporal stores, bit 2 write-through stores
-// (development switch MIFFT_DEBUG_STORE overrides the store side for A/B measurements)
 int stream_policy(int flags) {
     int nt = ((flags & MIFFT_FLAG_STREAM_SRC) ? 1 : 0) | ((flags & MIFFT_FLAG_STREAM_DST) ? 2 : 0);
     if (flags & MIFFT_FLAG_WRITE_THROUGH) nt = (nt & 1) | 4;
-    if (g_debug[MIFFT_DEBUG_STORE] == 1) nt = (nt & 1) | 2;
-    else if (g_debug[MIFFT_DEBUG_STORE] == 2) nt = (nt & 1) | 4;
-    else if (g_debug[MIFFT_DEBUG_STORE] == 3) nt = nt & 1;
-    return nt;
+    return store_override(nt);
 }
 
 void fill_args(const mifft_pass* p, const void* in0, const void* in1, void* out0, void* out1, mifft::TileArgs* pa) {
     mifft::TileArgs& a = *pa;
-    const bool split = p->layout == MIFFT_SPLIT && !(p->flags & MIFFT_FLAG_SRC_INTERLEAVED);
-    const bool split_out = p->layout == MIFFT_SPLIT && !(p->flags & MIFFT_FLAG_DST_INTERLEAVED);
     a.in0 = in0;
     a.in1 = in1;
     a.out0 = out0;
@@ -142,8 +211,8 @@ void fill_args(const mifft_pass* p, const void* in0, const void* in1, void* out0
         a.logS = 0;
     }
     a.tw_shift = p->tw_shift;
-    a.split = split ? 1 : 0;
-    a.split_out = split_out ? 1 : 0;
+    a.split = planes_in(p) ? 1 : 0;
+    a.split_out = planes_out(p) ? 1 : 0;
     a.inverse = p->inverse ? 1 : 0;
     a.has_tw = (p->kind == MIFFT_PASS_COL && p->M > 1) ? 1 : 0;
     a.nt = stream_policy(p->flags);
@@ -182,15 +251,9 @@ long long wave_bytes(const mifft_pass* p, const mifft::TileArgs* a) {   // bytes
     return a->total * p->L * (p->precision == MIFFT_F64 ? 16ll : 8ll);
 }
 
-// which form a fixed N-D shape runs: two work-groups per transform (fft_nd2z.hip) for the one-tile-per-CU shapes wherever that kernel
-// exists (it is only instantiated where it measured faster, at 32 MiB and at 1 GiB per side), for the two-per-CU shapes in SMALL launches
-// only -- the plan marks those with MIFFT_FLAG_WRITE_THROUGH (up to half the last-level cache per side).  A/B: MIFFT_DEBUG_ALT_ROWS = 6 never
-bool nd2z_preferred(bool f64, int x, int y, int z, bool small_launch) {
-    return g_debug[MIFFT_DEBUG_ALT_ROWS] != 6 && mifft_nd2z(f64 ? 1 : 0, x, y, z, nullptr, nullptr, small_launch ? 1 : 2) == 0;
-}
-
-// the stage list of the run-time-shaped N-D kernel (fft_nd.hpp) for the axes dims (x, y, z): axis geometry, radices, nstages;
-// -1 if it needs more than kNdMaxStages stages
+// the stage list of the run-time-shaped N-D kernel (fft_nd.hpp) for the axes dims (x, y, z): axis geometry, radices, nstages, and the
+// register edge -- the last stage of all writes runs of (L / radix) * S points, straight to HBM when that is >= 128 bytes (interleaved
+// output only: the caller clears edge_out for planes); -1 if it needs more than kNdMaxStages stages
 int nd_stage_list(const long long dims[3], bool f64, mifft::NdArgs* a) {
     int logs = 0, ns = 0;
     for (int ax = 0; ax < 3; ++ax) {
@@ -210,165 +273,98 @@ int nd_stage_list(const long long dims[3], bool f64, mifft::NdArgs* a) {
         }
     }
     a->nstages = ns;
+    if (ns >= 1) {
+        const int axn = a->st_axis[ns - 1];
+        a->edge_out = ((dims[axn] / a->st_radix[ns - 1]) << a->logS[axn]) * (f64 ? 16 : 8) >= 128 ? 1 : 0;
+    }
     return 0;
 }
 
-int launch_nd(const mifft_pass* p, const void* in0, const void* in1, void* out0, void* out1, hipStream_t s) {
-    // fixed-shape kernels (fft_nd2.hpp) for the common shapes, interleaved on both sides
-    // the run-time-shaped kernel only: the development switch, or variant 1 of the pass (the plan asks for it where that kernel measured
-    // faster than the shape's fixed instance: pyfft_amd/tuning_gfx950.json, "nd_generic")
-    const bool no_nd2 = g_debug[MIFFT_DEBUG_NO_ND2] != 0 || p->variant == 1;
+// The kernel form (MIFFT_ND_KERNEL_*) a validated ND pass runs -- a pure function of the descriptor, of which of the two buffer pairs
+// alias (bit 0: in0 == out0, bit 1: in1 == out1) and of the calling thread's development switches -- or a negative error code with its
+// message.  The planes of a side that has them are never null here (mifft_launch_pass refuses that first), so the forms ask for none.
+int select_nd(const mifft_pass* p, int aliased) {
+    const bool f64 = p->precision == MIFFT_F64, small_launch = (p->flags & MIFFT_FLAG_WRITE_THROUGH) != 0;
+    const int x = p->L, y = (int)p->M, z = (int)p->S;
+    const bool interleaved = !planes_in(p) && !planes_out(p), planes = planes_in(p) && planes_out(p);
     // the (16, 16) fp32 plane, interleaved: wave-autonomous kernel (no LDS, DPP exchange; csrc/fft_wave.hpp)
     // -- measured slower than the fixed-shape LDS kernel at the reference's 32 MiB buffer (0.62 vs 0.68 of the roofline) and
     // equal at 128 MiB (profiles/r02_h_small_n.log), so it only runs on request (MIFFT_DEBUG_FORCE_WAVE; parity-tested)
-    if (p->precision == MIFFT_F32 && p->L == 16 && p->M == 16 && p->S == 1 && g_debug[MIFFT_DEBUG_FORCE_WAVE] &&
-        (p->layout != MIFFT_SPLIT || ((p->flags & MIFFT_FLAG_SRC_INTERLEAVED) && (p->flags & MIFFT_FLAG_DST_INTERLEAVED)))) {
+    if (!f64 && x == 16 && y == 16 && z == 1 && g_debug[MIFFT_DEBUG_FORCE_WAVE] && interleaved) return MIFFT_ND_KERNEL_WAVE;
+    // variant 1 of the pass: the run-time-shaped kernel only (the plan asks for it where that kernel measured faster than the shape's
+    // fixed instance: pyfft_amd/tuning_gfx950.json, "nd_generic")
+    if (p->variant != 1) {
+        if (interleaved) {
+            // the one-tile-per-CU shapes always, the two-per-CU shapes in small launches, and shapes without a fixed instance
+            const bool have_nd2 = nd2_instance(f64, x, y, z);
+            if (!(aliased & 1) && nd2z_gate(f64, x, y, z, have_nd2 && !small_launch ? 2 : 1)) return MIFFT_ND_KERNEL_ND2Z;
+            if (have_nd2 && g_debug[MIFFT_DEBUG_NO_ND2] == 0) return MIFFT_ND_KERNEL_ND2;
+        }
+        if (planes && !(aliased & 3) && nd2zp_gate(f64, x, y, z, 1)) return MIFFT_ND_KERNEL_ND2ZP;
+        if (planes && nd2p_gate(f64, x, y, z, small_launch ? 2 : 1)) return MIFFT_ND_KERNEL_ND2P;
+        if (planes_in(p) && nd2t_gate(f64, x, y, z, 128)) return MIFFT_ND_KERNEL_ND2T;
+    }
+    if ((long long)p->L * p->M * p->S > mifft_nd_max_points(f64))
+        return set_err(MIFFT_E_UNSUPPORTED, "ND pass %d x %d x %d: this shape has a one-launch kernel out of place only, for interleaved data or planes on both sides "
+                       "(several work-groups per transform, mifft_nd_shape_supported with MIFFT_VARIANT_OUT_OF_PLACE_ONLY / _SPLIT_OUT_OF_PLACE)",
+                       z, y, x);
+    return MIFFT_ND_KERNEL_ND;
+}
+
+int launch_nd(const mifft_pass* p, const void* in0, const void* in1, void* out0, void* out1, hipStream_t s) {
+    const int form = select_nd(p, (in0 == out0 ? 1 : 0) | (in1 == out1 ? 2 : 0));
+    if (form < 0) return form;
+    const bool f64 = p->precision == MIFFT_F64;
+    const int x = p->L, y = (int)p->M, z = (int)p->S;
+    if (form == MIFFT_ND_KERNEL_WAVE) {
         mifft::WaveArgs w;
         w.in = in0; w.out = out0;
         w.pieces = p->outer * 128;
         w.inverse = p->inverse ? 1 : 0;
         w.nt = stream_policy(p->flags);
         w.scale = p->scale;
-        const int rc = mifft_wave_16x16_launch(&w, wave_max_blocks(), s);
-        if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
-        return 0;
+        return hip_check((hipError_t)mifft_wave_16x16_launch(&w, wave_max_blocks(), s), "kernel launch");
     }
-    const bool f64nd = p->precision == MIFFT_F64;
-    const int have_nd2 = f64nd ? mifft_nd2_f64_supported((int)p->L, (int)p->M, (int)p->S)
-                               : mifft_nd2_f32_supported((int)p->L, (int)p->M, (int)p->S);
-    const bool inter_both = p->layout != MIFFT_SPLIT || ((p->flags & MIFFT_FLAG_SRC_INTERLEAVED) && (p->flags & MIFFT_FLAG_DST_INTERLEAVED));
-    // Several work-groups per transform (fft_nd2z.hpp, round 5; out of place only): the one-tile-per-CU shapes always, the two-per-CU
-    // shapes in small launches, and shapes of FOUR two-per-CU tiles, which have no other one-launch kernel (the plan only builds such a
-    // pass for its out-of-place executes)
-    if (inter_both && !no_nd2 && in0 != out0 &&
-        (have_nd2 == 0 ? nd2z_preferred(f64nd, (int)p->L, (int)p->M, (int)p->S, (p->flags & MIFFT_FLAG_WRITE_THROUGH) != 0)
-                       : mifft_nd2z(f64nd ? 1 : 0, (int)p->L, (int)p->M, (int)p->S, nullptr, nullptr, 1) == 0)) {
-        mifft::TileArgs t;
-        memset(&t, 0, sizeof(t));
-        t.in0 = in0; t.out0 = out0;
-        t.tw_L = p->tw_L; t.tw_lo = p->tw_lo; t.tw_hi = p->tw_hi;
-        t.total = p->outer * p->L * p->M * p->S;
-        t.inverse = p->inverse ? 1 : 0;
-        t.scale = p->scale;
-        t.nt = stream_policy(p->flags);
-        const int rz = mifft_nd2z(f64nd ? 1 : 0, (int)p->L, (int)p->M, (int)p->S, &t, s, 0);
-        if (rz == -1) return set_err(MIFFT_E_INVALID, "grid too large");
-        if (rz != 0) return hip_check((hipError_t)rz, "kernel launch");
-        return 0;
+    if (form == MIFFT_ND_KERNEL_ND) {
+        mifft::NdArgs a;
+        memset(&a, 0, sizeof(a));
+        a.in0 = in0; a.in1 = in1; a.out0 = out0; a.out1 = out1;
+        a.tw[0] = p->tw_L; a.tw[1] = p->tw_lo; a.tw[2] = p->tw_hi;
+        const long long dims[3] = {p->L, p->M, p->S};
+        a.total = p->outer * dims[0] * dims[1] * dims[2];
+        if (nd_stage_list(dims, f64, &a) != 0) return set_err(MIFFT_E_UNSUPPORTED, "ND pass: too many stages");
+        a.split = planes_in(p) ? 1 : 0;
+        a.split_out = planes_out(p) ? 1 : 0;
+        if (a.split_out) a.edge_out = 0;
+        a.inverse = p->inverse ? 1 : 0;
+        a.scale = p->scale;
+        // small launches: write-through stores of the result (the store phase -- planes always go through it; an interleaved result that
+        // leaves by the register edge keeps plain stores).  MIFFT_NARROW_TILES = 1: off (A/B)
+        a.wt = ((stream_policy(p->flags) & 4) && g_debug[MIFFT_DEBUG_NARROW_TILES] != 1) ? 1 : 0;
+        return launched(mifft_nd_launch(f64 ? 1 : 0, dims[0] * dims[1] * dims[2], &a, s));
     }
-    if (have_nd2 == 0 &&
-        (p->layout != MIFFT_SPLIT || ((p->flags & MIFFT_FLAG_SRC_INTERLEAVED) && (p->flags & MIFFT_FLAG_DST_INTERLEAVED))) &&
-        !no_nd2) {
-        mifft::TileArgs t;
-        memset(&t, 0, sizeof(t));
-        t.in0 = in0; t.out0 = out0;
-        t.tw_L = p->tw_L; t.tw_lo = p->tw_lo; t.tw_hi = p->tw_hi;
-        t.total = p->outer * p->L * p->M * p->S;
-        t.inverse = p->inverse ? 1 : 0;
-        t.scale = p->scale;
-        t.nt = stream_policy(p->flags);
-        const int rc = f64nd ? mifft_nd2_f64_launch((int)p->L, (int)p->M, (int)p->S, &t, s)
-                             : mifft_nd2_f32_launch((int)p->L, (int)p->M, (int)p->S, &t, s);
-        if (rc == -1) return set_err(MIFFT_E_INVALID, "grid too large");
-        if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
-        return 0;
-    }
-    // split-complex planes on both sides (a single-pass N-D plan): the fixed-shape stage chain exists for planes in its TILED form
-    // (fft_nd2t.hpp, second batch of round 4) -- a dense batch is the tiling with one tile per "parent".  (128, 128) planes at 1 GiB:
-    // 0.471 on the run-time-shaped kernel below -> 0.653 (interleaved fixed-shape kernel 0.700), (64, 64) 0.535 -> 0.597, fp64 16^3
-    // 0.510 -> 0.584; shapes whose x rows are shorter than 128 bytes per plane stay below -- fp32 (16, 16) 0.717 against 0.460, 16^3 0.674
-    // against 0.475: their tiles move scalars over short runs (profiles/r04_at_rows_split.log)
-    // (planes in, interleaved out -- the plane pass of a split-complex multi-pass plan -- likewise: fft_nd2t_split_in.hip)
-    // Round 6: planes on BOTH sides of a published shape: the dense kernel that moves 16 bytes per lane and plane (fft_nd2p.hpp); the tiled
-    // kernel below moves one scalar per lane and plane through the tiling's address arithmetic (0.69-0.86 of the interleaved twin at 1 GiB).
-    // MIFFT_DEBUG_ALT_ROWS = 7: the tiled kernel (A/B)
-    // ... and its one-tile-per-CU shapes as two half-size work-groups per transform, out of place (fft_nd2zp.hpp; MIFFT_DEBUG_ALT_ROWS = 6:
-    // never several work-groups per transform, as for interleaved data)
-    if (p->layout == MIFFT_SPLIT && !(p->flags & (MIFFT_FLAG_SRC_INTERLEAVED | MIFFT_FLAG_DST_INTERLEAVED)) && !no_nd2 && in1 && out1 &&
-        in0 != out0 && in1 != out1 && g_debug[MIFFT_DEBUG_NARROW_TILES] != 1 && g_debug[MIFFT_DEBUG_ALT_ROWS] != 7 &&
-        g_debug[MIFFT_DEBUG_ALT_ROWS] != 6 && mifft_nd2zp(f64nd ? 1 : 0, (int)p->L, (int)p->M, (int)p->S, nullptr, nullptr, 1) == 0) {
-        mifft::TileArgs t;
-        memset(&t, 0, sizeof(t));
-        t.in0 = in0; t.in1 = in1; t.out0 = out0; t.out1 = out1;
-        t.split = 1; t.split_out = 1;
-        t.tw_L = p->tw_L; t.tw_lo = p->tw_lo; t.tw_hi = p->tw_hi;
-        t.total = p->outer * p->L * p->M * p->S;
-        t.inverse = p->inverse ? 1 : 0;
-        t.scale = p->scale;
-        t.nt = stream_policy(p->flags);
-        const int rc = mifft_nd2zp(f64nd ? 1 : 0, (int)p->L, (int)p->M, (int)p->S, &t, s, 0);
-        if (rc == -1) return set_err(MIFFT_E_INVALID, "grid too large");
-        if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
-        return 0;
-    }
-    if (p->layout == MIFFT_SPLIT && !(p->flags & (MIFFT_FLAG_SRC_INTERLEAVED | MIFFT_FLAG_DST_INTERLEAVED)) && !no_nd2 && in1 && out1 &&
-        g_debug[MIFFT_DEBUG_NARROW_TILES] != 1 && g_debug[MIFFT_DEBUG_ALT_ROWS] != 7 &&
-        mifft_nd2p(f64nd ? 1 : 0, (int)p->L, (int)p->M, (int)p->S, nullptr, nullptr, (p->flags & MIFFT_FLAG_WRITE_THROUGH) ? 2 : 1) == 0) {
-        mifft::TileArgs t;
-        memset(&t, 0, sizeof(t));
-        t.in0 = in0; t.in1 = in1; t.out0 = out0; t.out1 = out1;
-        t.split = 1; t.split_out = 1;
-        t.tw_L = p->tw_L; t.tw_lo = p->tw_lo; t.tw_hi = p->tw_hi;
-        t.total = p->outer * p->L * p->M * p->S;
-        t.inverse = p->inverse ? 1 : 0;
-        t.scale = p->scale;
-        t.nt = stream_policy(p->flags);
-        const int rc = mifft_nd2p(f64nd ? 1 : 0, (int)p->L, (int)p->M, (int)p->S, &t, s, 0);
-        if (rc == -1) return set_err(MIFFT_E_INVALID, "grid too large");
-        if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
-        return 0;
-    }
-    const bool planes_in_only = p->layout == MIFFT_SPLIT && !(p->flags & MIFFT_FLAG_SRC_INTERLEAVED) && (p->flags & MIFFT_FLAG_DST_INTERLEAVED);
-    if (p->layout == MIFFT_SPLIT && !(p->flags & MIFFT_FLAG_SRC_INTERLEAVED) && !no_nd2 && in1 && (out1 || planes_in_only) &&
-        g_debug[MIFFT_DEBUG_NARROW_TILES] != 1 && p->L * (f64nd ? 8 : 4) >= 128 &&
-        mifft_nd2t_split(f64nd, (int)p->L, (int)p->M, (int)p->S, nullptr, nullptr, nullptr, 1) == 0) {
-        mifft::TileArgs t;
-        memset(&t, 0, sizeof(t));
-        t.in0 = in0; t.in1 = in1; t.out0 = out0; t.out1 = planes_in_only ? nullptr : out1;
-        t.split = 1;
-        t.split_out = planes_in_only ? 0 : 1;
-        t.nt = stream_policy(p->flags) & 4;      // (the kernel knows the write-through form of the small launches only)
-        t.tw_L = p->tw_L; t.tw_lo = p->tw_lo; t.tw_hi = p->tw_hi;
-        t.inverse = p->inverse ? 1 : 0;
-        t.scale = p->scale;
-        mifft::TiledGeom g;
-        g.pitch_y = p->L; g.pitch_z = (long long)p->L * p->M; g.parent = (long long)p->L * p->M * p->S; g.tiles = p->outer;
-        g.cx = g.cy = g.cz = 1;
-        const int rc = (planes_in_only ? mifft_nd2t_split_in : mifft_nd2t_split)(f64nd, (int)p->L, (int)p->M, (int)p->S, &t, &g, s, 0);
-        if (rc == -1) return set_err(MIFFT_E_INVALID, "grid too large");
-        if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
-        return 0;
-    }
-    if ((long long)p->L * p->M * p->S > mifft_nd_max_points(f64nd))
-        return set_err(MIFFT_E_UNSUPPORTED, "ND pass %d x %d x %d: this shape has a one-launch kernel out of place only, for interleaved data or planes on both sides "
-                       "(several work-groups per transform, mifft_nd_shape_supported with MIFFT_VARIANT_OUT_OF_PLACE_ONLY / _SPLIT_OUT_OF_PLACE)",
-                       (int)p->S, (int)p->M, (int)p->L);
-    mifft::NdArgs a;
-    memset(&a, 0, sizeof(a));
-    a.in0 = in0; a.in1 = in1; a.out0 = out0; a.out1 = out1;
-    a.tw[0] = p->tw_L; a.tw[1] = p->tw_lo; a.tw[2] = p->tw_hi;
-    const long long dims[3] = {p->L, p->M, p->S};
-    a.total = p->outer * dims[0] * dims[1] * dims[2];
-    const bool f64 = p->precision == MIFFT_F64;
-    if (nd_stage_list(dims, f64, &a) != 0) return set_err(MIFFT_E_UNSUPPORTED, "ND pass: too many stages");
-    const int ns = a.nstages;
-    a.split = (p->layout == MIFFT_SPLIT && !(p->flags & MIFFT_FLAG_SRC_INTERLEAVED)) ? 1 : 0;
-    a.split_out = (p->layout == MIFFT_SPLIT && !(p->flags & MIFFT_FLAG_DST_INTERLEAVED)) ? 1 : 0;
-    a.inverse = p->inverse ? 1 : 0;
-    a.scale = p->scale;
-    // register edge: the last stage of all writes runs of (L / radix) * S points; straight to HBM when that is >= 128 bytes
-    if (ns >= 1) {
-        const int axn = a.st_axis[ns - 1];
-        const long long run_out = ((dims[axn] / a.st_radix[ns - 1]) << a.logS[axn]) * (f64 ? 16 : 8);
-        a.edge_out = (!a.split_out && run_out >= 128) ? 1 : 0;
-    }
-    // small launches: write-through stores of the result (the store phase -- planes always go through it; an interleaved result that
-    // leaves by the register edge keeps plain stores).  MIFFT_NARROW_TILES = 1: off (A/B)
-    a.wt = ((stream_policy(p->flags) & 4) && g_debug[MIFFT_DEBUG_NARROW_TILES] != 1) ? 1 : 0;
-    const int rc = mifft_nd_launch(f64 ? 1 : 0, dims[0] * dims[1] * dims[2], &a, s);
-    if (rc == -1) return set_err(MIFFT_E_INVALID, "grid too large");
-    if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
-    return 0;
+    mifft::TileArgs t;
+    memset(&t, 0, sizeof(t));
+    t.in0 = in0; t.in1 = in1; t.out0 = out0; t.out1 = out1;
+    t.split = planes_in(p) ? 1 : 0;
+    t.split_out = planes_out(p) ? 1 : 0;
+    t.tw_L = p->tw_L; t.tw_lo = p->tw_lo; t.tw_hi = p->tw_hi;
+    t.total = p->outer * p->L * p->M * p->S;
+    t.inverse = p->inverse ? 1 : 0;
+    t.scale = p->scale;
+    t.nt = stream_policy(p->flags);
+    if (form == MIFFT_ND_KERNEL_ND2Z) return launched(mifft_nd2z(f64 ? 1 : 0, x, y, z, &t, s, 0));
+    if (form == MIFFT_ND_KERNEL_ND2) return launched(f64 ? mifft_nd2_f64_launch(x, y, z, &t, s) : mifft_nd2_f32_launch(x, y, z, &t, s));
+    if (form == MIFFT_ND_KERNEL_ND2ZP) return launched(mifft_nd2zp(f64 ? 1 : 0, x, y, z, &t, s, 0));
+    if (form == MIFFT_ND_KERNEL_ND2P) return launched(mifft_nd2p(f64 ? 1 : 0, x, y, z, &t, s, 0));
+    // the tiled kernel on a dense batch: one tile per "parent"; it counts tiles, not points, and knows the write-through form of the
+    // small launches only
+    t.total = 0;
+    t.nt &= 4;
+    mifft::TiledGeom g;
+    g.pitch_y = p->L; g.pitch_z = (long long)p->L * p->M; g.parent = (long long)p->L * p->M * p->S; g.tiles = p->outer;
+    g.cx = g.cy = g.cz = 1;
+    return launched((planes_out(p) ? mifft_nd2t_split : mifft_nd2t_split_in)(f64, x, y, z, &t, &g, s, 0));
 }
 
 int dispatch(const mifft_pass* p, const mifft::TileArgs* a, hipStream_t s, int query_only) {
@@ -389,8 +385,7 @@ int dispatch(const mifft_pass* p, const mifft::TileArgs* a, hipStream_t s, int q
         w.nt = a->nt;
         w.scale = a->scale;
         rc = mifft_wave_launch(p->precision == MIFFT_F64, p->L, &w, wave_max_blocks(), s);
-        if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
-        return 0;
+        return hip_check((hipError_t)rc, "kernel launch");
     }
     if (p->kind == MIFFT_PASS_COL)
         rc = p->precision == MIFFT_F32 ? mifft_dispatch_col_f32(p->L, tr, p->variant, a, s, query_only)
@@ -400,9 +395,7 @@ int dispatch(const mifft_pass* p, const mifft::TileArgs* a, hipStream_t s, int q
                                        : mifft_dispatch_row_f64(p->L, p->variant, a, s, query_only);
     if (rc == MIFFT_E_UNSUPPORTED)
         return set_err(rc, "no compiled kernel for kind=%d precision=%d L=%d variant=%d", p->kind, p->precision, p->L, p->variant);
-    if (rc == -1) return set_err(MIFFT_E_INVALID, "grid too large");
-    if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
-    return 0;
+    return launched(rc);
 }
 
 // ---- pass pairs (fft_pair.hpp) -------------------------------------------------------------------------------------
@@ -506,8 +499,8 @@ int fill_ctl(mifft::FusedCtl* c, const mifft_fused_sync* sync, long long outer, 
              hipStream_t stream, const char* who) {
     static_assert(mifft::kFusedCS == MIFFT_FUSED2_COUNTER_STRIDE, "counter stride");
     if (!sync || !sync->counters) return set_err(MIFFT_E_INVALID, "%s: null counters", who);
-    if (((uintptr_t)sync->counters | (uintptr_t)sync->counters_next) & 255) return set_err(MIFFT_E_INVALID, "%s: counter buffers must be 256-byte aligned", who);
-    if ((uintptr_t)sync->error_word & 3) return set_err(MIFFT_E_INVALID, "%s: misaligned error word", who);
+    if (misaligned(255, {sync->counters, sync->counters_next})) return set_err(MIFFT_E_INVALID, "%s: counter buffers must be 256-byte aligned", who);
+    if (misaligned(3, {sync->error_word})) return set_err(MIFFT_E_INVALID, "%s: misaligned error word", who);
     if (sync->counters_next == sync->counters) return set_err(MIFFT_E_INVALID, "%s: counters_next must be a second buffer", who);
     if (outer > 0x3fffffff) return set_err(MIFFT_E_INVALID, "%s: batch too large", who);
     if (sync->counters_next) {
@@ -536,7 +529,7 @@ int fill_ctl(mifft::FusedCtl* c, const mifft_fused_sync* sync, long long outer, 
         hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing(stream, &st) == hipSuccess && st == hipStreamCaptureStatusActive) {
             const int rz = mifft_aux_zero_launch(sync->counters, MIFFT_FUSED2_COUNTER_BYTES(outer), stream);
-            return rz == 0 ? 0 : hip_check((hipError_t)rz, "kernel launch");
+            return hip_check((hipError_t)rz, "kernel launch");
         }
         return hip_check(hipMemsetAsync(sync->counters, 0, MIFFT_FUSED2_COUNTER_BYTES(outer), stream), "hipMemsetAsync");
     }
@@ -701,31 +694,21 @@ int mifft_event_elapsed_ms(float* ms, mifft_event_t start, mifft_event_t stop) {
 int mifft_nd_max_points_for(int32_t precision) { return mifft_nd_max_points(precision == MIFFT_F64); }
 
 int mifft_nd_shape_supported(int32_t precision, int32_t x, int32_t y, int32_t z, int32_t variant) {
-    if (precision != MIFFT_F32 && precision != MIFFT_F64) return MIFFT_E_UNSUPPORTED;
+    if (bad_precision(precision)) return MIFFT_E_UNSUPPORTED;
     if (x < 1 || y < 1 || z < 1 || (x & (x - 1)) || (y & (y - 1)) || (z & (z - 1))) return MIFFT_E_UNSUPPORTED;
     const long long n = (long long)x * y * z;
     if (n <= mifft_nd_max_points(precision == MIFFT_F64)) return 0;
-    if (variant == MIFFT_VARIANT_SPLIT_ONLY)      // planes on both sides: the tiled fixed-shape kernel with one tile per parent (launch_nd)
-        // (x rows of >= 256 bytes per plane: fp64 (128, 128) 0.374 as two passes -> 0.568, (16, 32, 32) 0.338 -> 0.499; fp32 32^3, 128-byte
-        // rows, measured 0.285 against 0.307 for its two passes and keeps them -- profiles/r04_at_rows_split.log)
-        // (round 6: or a dense planes instance of fft_nd2p.hip -- fp32 (16, 16, 128), 32^3)
-        return (g_debug[MIFFT_DEBUG_NARROW_TILES] != 1 && g_debug[MIFFT_DEBUG_NO_ND2] == 0 &&
-                ((x * (precision == MIFFT_F64 ? 8 : 4) >= 256 && mifft_nd2t_split(precision == MIFFT_F64, x, y, z, nullptr, nullptr, nullptr, 1) == 0) ||
-                 (g_debug[MIFFT_DEBUG_ALT_ROWS] != 7 && mifft_nd2p(precision == MIFFT_F64 ? 1 : 0, x, y, z, nullptr, nullptr, 1) == 0))) ? 0 : MIFFT_E_UNSUPPORTED;
-    if (variant == MIFFT_VARIANT_OUT_OF_PLACE_ONLY || variant == MIFFT_VARIANT_OUT_OF_PLACE_ANY_SIZE)
-        // interleaved on both sides AND out of place: several work-groups per transform (fft_nd2z.hpp)
-        return (g_debug[MIFFT_DEBUG_NO_ND2] == 0 && g_debug[MIFFT_DEBUG_ALT_ROWS] != 6 &&
-                mifft_nd2z(precision == MIFFT_F64 ? 1 : 0, x, y, z, nullptr, nullptr, variant == MIFFT_VARIANT_OUT_OF_PLACE_ONLY ? 1 : 2) == 0)
-                   ? 0 : MIFFT_E_UNSUPPORTED;
-    if (variant == MIFFT_VARIANT_SPLIT_OUT_OF_PLACE || variant == MIFFT_VARIANT_SPLIT_OUT_OF_PLACE_ANY_SIZE)
-        // planes on both sides AND out of place: several work-groups per transform on 16-byte plane accesses (fft_nd2zp.hpp)
-        return (g_debug[MIFFT_DEBUG_NO_ND2] == 0 && g_debug[MIFFT_DEBUG_ALT_ROWS] != 6 && g_debug[MIFFT_DEBUG_ALT_ROWS] != 7 &&
-                g_debug[MIFFT_DEBUG_NARROW_TILES] != 1 &&
-                mifft_nd2zp(precision == MIFFT_F64 ? 1 : 0, x, y, z, nullptr, nullptr, variant == MIFFT_VARIANT_SPLIT_OUT_OF_PLACE ? 1 : 2) == 0)
-                   ? 0 : MIFFT_E_UNSUPPORTED;
-    if (variant != MIFFT_VARIANT_INTERLEAVED_ONLY) return MIFFT_E_UNSUPPORTED;
-    const int rc = precision == MIFFT_F64 ? mifft_nd2_f64_supported(x, y, z) : mifft_nd2_f32_supported(x, y, z);
-    return rc == 0 ? 0 : MIFFT_E_UNSUPPORTED;
+    const bool f64 = precision == MIFFT_F64;
+    bool ok = false;
+    if (variant == MIFFT_VARIANT_SPLIT_ONLY)      // planes on both sides: the tiled kernel where it beats two passes, or a dense planes instance
+        ok = nd2t_gate(f64, x, y, z, 256) || nd2p_gate(f64, x, y, z, 1);
+    else if (variant == MIFFT_VARIANT_OUT_OF_PLACE_ONLY || variant == MIFFT_VARIANT_OUT_OF_PLACE_ANY_SIZE)      // interleaved AND out of place
+        ok = nd2z_gate(f64, x, y, z, variant == MIFFT_VARIANT_OUT_OF_PLACE_ONLY ? 1 : 2);
+    else if (variant == MIFFT_VARIANT_SPLIT_OUT_OF_PLACE || variant == MIFFT_VARIANT_SPLIT_OUT_OF_PLACE_ANY_SIZE)   // planes AND out of place
+        ok = nd2zp_gate(f64, x, y, z, variant == MIFFT_VARIANT_SPLIT_OUT_OF_PLACE ? 1 : 2);
+    else if (variant == MIFFT_VARIANT_INTERLEAVED_ONLY)
+        ok = nd2_instance(f64, x, y, z);
+    return ok ? 0 : MIFFT_E_UNSUPPORTED;
 }
 
 int mifft_pass_supported(int32_t kind, int32_t precision, int32_t L, int32_t variant) {
@@ -745,22 +728,34 @@ int mifft_pass_supported(int32_t kind, int32_t precision, int32_t L, int32_t var
     return dispatch(&p, nullptr, nullptr, 1);
 }
 
+// what mifft_launch_pass checks once the descriptor is valid and before it looks at a pointer
+static int check_strides(const mifft_pass* p) {
+    if ((p->outer_stride_in | p->outer_stride_out) & 1) return set_err(MIFFT_E_INVALID, "outer strides must be even");
+    return 0;
+}
+
+int mifft_nd_kernel(const mifft_pass* p, int32_t aliased) {
+    int rc = validate(p);
+    if (rc) return rc;
+    if (p->kind != MIFFT_PASS_ND) return set_err(MIFFT_E_INVALID, "mifft_nd_kernel: not an ND pass");
+    rc = check_strides(p);
+    if (rc) return rc;
+    return select_nd(p, planes_in(p) && planes_out(p) ? aliased & 3 : aliased & 1);
+}
+
 int mifft_launch_pass(const mifft_pass* p, const void* in0, const void* in1, void* out0, void* out1, mifft_stream_t stream) {
     int rc = validate(p);
     if (rc) return rc;
     if (!in0 || !out0) return set_err(MIFFT_E_INVALID, "null data buffer");
-    const bool split_in = p->layout == MIFFT_SPLIT && !(p->flags & MIFFT_FLAG_SRC_INTERLEAVED);
-    const bool split_out = p->layout == MIFFT_SPLIT && !(p->flags & MIFFT_FLAG_DST_INTERLEAVED);
-    const bool split = split_in;
+    const bool split_in = planes_in(p), split_out = planes_out(p);
     if ((split_in && !in1) || (split_out && !out1)) return set_err(MIFFT_E_INVALID, "split layout needs imaginary planes");
     if (p->layout != MIFFT_SPLIT && (in1 || out1)) return set_err(MIFFT_E_INVALID, "interleaved layout takes no imaginary planes");
     if (!split_in) in1 = nullptr;
     if (!split_out) out1 = nullptr;
-    const uintptr_t align_mask = 15;
-    if (((uintptr_t)in0 | (uintptr_t)out0 | (uintptr_t)in1 | (uintptr_t)out1) & align_mask)
-        return set_err(MIFFT_E_INVALID, "data buffers must be 16-byte aligned");
-    if ((p->outer_stride_in | p->outer_stride_out) & 1) return set_err(MIFFT_E_INVALID, "outer strides must be even");
-    if (p->kind == MIFFT_PASS_COL && p->M > 1 && (in0 == out0 || (split && split_out && in1 == out1)))
+    if (misaligned(15, {in0, out0, in1, out1})) return set_err(MIFFT_E_INVALID, "data buffers must be 16-byte aligned");
+    rc = check_strides(p);
+    if (rc) return rc;
+    if (p->kind == MIFFT_PASS_COL && p->M > 1 && (in0 == out0 || (split_in && split_out && in1 == out1)))
         return set_err(MIFFT_E_INVALID, "a COL pass with M > 1 cannot run in place");
     if (p->outer == 0) return 0;
 
@@ -794,7 +789,7 @@ int mifft_pair_split(int32_t precision, int32_t layout, int32_t x, int32_t y, in
 }
 
 int mifft_pair_kernel_supported(int32_t precision, int32_t layout, int32_t kind, int32_t k0, int32_t k1, int32_t k2) {
-    if ((precision != MIFFT_F32 && precision != MIFFT_F64) || (layout != MIFFT_INTERLEAVED && layout != MIFFT_SPLIT) || (kind != 0 && kind != 1))
+    if (bad_precision(precision) || (layout != MIFFT_INTERLEAVED && layout != MIFFT_SPLIT) || (kind != 0 && kind != 1))
         return MIFFT_E_UNSUPPORTED;
     if (g_debug[MIFFT_DEBUG_PAIR] == 1) return MIFFT_E_UNSUPPORTED;      // (as mifft_pair_split: the switch acts when a plan is built)
     const int key[3] = {k0, k1, k2};
@@ -819,7 +814,7 @@ int mifft_launch_pass_pair(const mifft_pass* p0, const mifft_pass* p1, const voi
         return set_err(MIFFT_E_UNSUPPORTED, "pass pair: not a (ROW x, COL y) / (COL y, COL z) pair of a dense batch with an interleaved intermediate");
     if (!in0 || !out0) return set_err(MIFFT_E_INVALID, "null data buffer");
     if (split && ((kind == 0 && !in1) || (kind == 1 && !out1))) return set_err(MIFFT_E_INVALID, "split layout needs imaginary planes");
-    if (((uintptr_t)in0 | (uintptr_t)out0 | (uintptr_t)in1 | (uintptr_t)out1) & 15) return set_err(MIFFT_E_INVALID, "data buffers must be 16-byte aligned");
+    if (misaligned(15, {in0, out0, in1, out1})) return set_err(MIFFT_E_INVALID, "data buffers must be 16-byte aligned");
     if (kind == 0 && in0 == out0) return set_err(MIFFT_E_INVALID, "the (ROW x, COL y) pair cannot run in place");
     if (p1->outer == 0) return 0;
     int width = 0;
@@ -847,16 +842,9 @@ int mifft_launch_pass_pair(const mifft_pass* p0, const mifft_pass* p1, const voi
     // streamed sides: non-temporal loads of the plan's input, PLAIN stores on both launches (BASELINE config 4 at batch 64, one
     // box: plain 13.31 ms, write-through 14.44 ms; non-temporal stores measured below plain ones at batch 16 --
     // profiles/r03_c_store_policy.log)
-    a.nt = (p0->flags & MIFFT_FLAG_STREAM_SRC) ? 1 : 0;
-    if (p1->flags & MIFFT_FLAG_WRITE_THROUGH) a.nt |= 4;
-    if (g_debug[MIFFT_DEBUG_STORE] == 1) a.nt = (a.nt & 1) | 2;
-    else if (g_debug[MIFFT_DEBUG_STORE] == 2) a.nt = (a.nt & 1) | 4;
-    else if (g_debug[MIFFT_DEBUG_STORE] == 3) a.nt = a.nt & 1;
+    a.nt = store_override(((p0->flags & MIFFT_FLAG_STREAM_SRC) ? 1 : 0) | ((p1->flags & MIFFT_FLAG_WRITE_THROUGH) ? 4 : 0));
     a.scale = p0->scale * p1->scale;
-    rc = pair_call(p0->precision, kind, key, split, &a, (hipStream_t)stream, 0, nullptr);
-    if (rc == -1) return set_err(MIFFT_E_INVALID, "grid too large");
-    if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
-    return 0;
+    return launched(pair_call(p0->precision, kind, key, split, &a, (hipStream_t)stream, 0, nullptr));
 }
 
 // one unit of a chain: a single pass, or a pass pair (MIFFT_FLAG_PAIR_WITH_NEXT on the first); *consumed = descriptors used
@@ -903,6 +891,10 @@ int mifft_launch_fused2(const mifft_pass* p0, const mifft_pass* p1, const void* 
     // 2-D form: the ROW pass (x axis, length nx) and the strided COL pass (y axis, length ny) of a 2-D plan, run as two
     // transposing column passes; fp32: nx, ny in {512, 1024, 2048} (split planes: squares only), fp64: 1024 x 1024
     const bool twod = p0->kind == MIFFT_PASS_ROW;
+    // split-complex fp32 2-D: the row-first kernel (fft_fused2r.hpp), (ny, nx) in {256, 512, 1024}^2 -- the chain's own order, ROW x from
+    // the planes, COL y to the planes, on the persistent list
+    const bool rowfirst = twod && !f64 && p0->layout == MIFFT_SPLIT && g_debug[MIFFT_DEBUG_NARROW_TILES] != 1 && !g_debug[MIFFT_DEBUG_NO_ROWFIRST] &&
+                          mifft_fused2r_f32(p1->L, p0->L, nullptr, 0, nullptr, 1) == 0;
     if (twod) {
         auto side = [](int L) { return L == 512 || L == 1024 || L == 2048; };
         auto side64 = [](int L) { return L == 512 || L == 1024; };
@@ -910,10 +902,7 @@ int mifft_launch_fused2(const mifft_pass* p0, const mifft_pass* p1, const void* 
         const bool small = p0->layout != MIFFT_SPLIT && (p0->L == 256 || p1->L == 256) &&
                            (f64 ? (p0->L <= 512 && p1->L <= 512 && p0->L >= 256 && p1->L >= 256)
                                 : (g_debug[MIFFT_DEBUG_NARROW_TILES] != 1 && mifft_fused2dw_f32(p1->L, p0->L, nullptr, 0, nullptr, 1, nullptr, nullptr) == 0));
-        // split-complex fp32: the row-first kernel (fft_fused2r.hpp), (ny, nx) in {256, 512, 1024}^2
-        const bool rowfirst_ok = !f64 && p0->layout == MIFFT_SPLIT && g_debug[MIFFT_DEBUG_NARROW_TILES] != 1 && !g_debug[MIFFT_DEBUG_NO_ROWFIRST] &&
-                                 mifft_fused2r_f32(p1->L, p0->L, nullptr, 0, nullptr, 1) == 0;
-        const bool okL = small || rowfirst_ok || (f64 ? (side64(p0->L) && side64(p1->L) && ((p0->L == 1024 && p1->L == 1024) || p0->layout != MIFFT_SPLIT))
+        const bool okL = small || rowfirst || (f64 ? (side64(p0->L) && side64(p1->L) && ((p0->L == 1024 && p1->L == 1024) || p0->layout != MIFFT_SPLIT))
                              : (side(p0->L) && side(p1->L) && (p0->L == p1->L || p0->layout != MIFFT_SPLIT)));
         if (p1->kind != MIFFT_PASS_COL || !okL || p1->S != p0->L || p1->M != 1 ||
             p0->outer != p1->outer * p1->L || p0->layout != p1->layout || p0->inverse != p1->inverse)
@@ -935,7 +924,7 @@ int mifft_launch_fused2(const mifft_pass* p0, const mifft_pass* p1, const void* 
     (void)ring1;  // the ring is always interleaved
     if (grid < 1) return set_err(MIFFT_E_INVALID, "fused2: grid >= 1");
     if (ring_slots < 2 || lag < 1 || lag >= ring_slots) return set_err(MIFFT_E_INVALID, "fused2: need 1 <= lag < ring_slots");
-    if (((uintptr_t)in0 | (uintptr_t)out0 | (uintptr_t)ring0 | (uintptr_t)in1 | (uintptr_t)out1) & 15)
+    if (misaligned(15, {in0, out0, ring0, in1, out1}))
         return set_err(MIFFT_E_INVALID, "data buffers must be 16-byte aligned");
     if (p1->outer == 0) return 0;
     const int64_t n = (int64_t)p0->L * p1->L;
@@ -944,9 +933,6 @@ int mifft_launch_fused2(const mifft_pass* p0, const mifft_pass* p1, const void* 
     fill_args(p1, ring0, nullptr, out0, out1, &f.p1);
     f.p0.ostride_out = n;  // ring slot pitch
     f.p1.ostride_in = n;
-    // split-complex fp32 2-D: the chain's own order -- ROW x from the planes, COL y to the planes -- on the persistent list
-    const bool rowfirst = twod && !f64 && p0->layout == MIFFT_SPLIT && g_debug[MIFFT_DEBUG_NARROW_TILES] != 1 && !g_debug[MIFFT_DEBUG_NO_ROWFIRST] &&
-                          mifft_fused2r_f32(p1->L, p0->L, nullptr, 0, nullptr, 1) == 0;
     if (rowfirst) {
         f.p0.nt = 4;                // the ring is written through (the consumers acquire it, fft_fused2.hpp)
         f.p0.scale = p0->scale;
@@ -998,17 +984,16 @@ int mifft_launch_fused2(const mifft_pass* p0, const mifft_pass* p1, const void* 
        : f64 ? mifft_fused3_f64_launch(p0->L, p1->L, &f, split ? 1 : 0, (unsigned)grid, (hipStream_t)stream)
              : mifft_fused2_f32_launch(p0->L, p1->L, &f, split ? 1 : 0, (unsigned)grid, (hipStream_t)stream);
     if (rc == MIFFT_E_UNSUPPORTED) return set_err(rc, "fused2: no kernel for %d x %d", p0->L, p1->L);
-    if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
-    return 0;
+    return hip_check((hipError_t)rc, "kernel launch");
 }
 
 int mifft_fused_pair_supported(int32_t precision, int32_t layout, int32_t x, int32_t y, int32_t z) {
-    if ((precision != MIFFT_F32 && precision != MIFFT_F64) || (layout != MIFFT_INTERLEAVED && layout != MIFFT_SPLIT)) return MIFFT_E_UNSUPPORTED;
+    if (bad_precision(precision) || (layout != MIFFT_INTERLEAVED && layout != MIFFT_SPLIT)) return MIFFT_E_UNSUPPORTED;
     return mifft_fusedp(precision == MIFFT_F64, layout == MIFFT_SPLIT, x, y, z, nullptr, 0, nullptr, 1, nullptr, nullptr, nullptr) == 0 ? 0 : MIFFT_E_UNSUPPORTED;
 }
 
 int mifft_fused_pair_split(int32_t precision, int32_t layout, int32_t x, int32_t y, int32_t z) {
-    if ((precision != MIFFT_F32 && precision != MIFFT_F64) || (layout != MIFFT_INTERLEAVED && layout != MIFFT_SPLIT)) return 0;
+    if (bad_precision(precision) || (layout != MIFFT_INTERLEAVED && layout != MIFFT_SPLIT)) return 0;
     int r0 = 0;
     if (mifft_fusedp(precision == MIFFT_F64, layout == MIFFT_SPLIT, x, y, z, nullptr, 0, nullptr, 1, &r0, nullptr, nullptr) != 0) return 0;
     return r0;
@@ -1036,7 +1021,7 @@ int mifft_launch_fused_pair(const mifft_pass* passes, const void* in0, const voi
     if (mifft_fusedp(f64, split ? 1 : 0, nx, ny, nz, nullptr, 0, nullptr, 1, &r0, &tiles0, &tiles1) != 0 || r0 != py0->L)
         return set_err(MIFFT_E_UNSUPPORTED, "fused pair: no kernel for %d x %d x %d with y = %d x %lld%s", nz, ny, nx, py0->L, (long long)py0->M, split ? " (split planes)" : "");
     if (!in0 || !out0 || !ring0 || (split && (!in1 || !out1))) return set_err(MIFFT_E_INVALID, "fused pair: null buffer");
-    if (((uintptr_t)in0 | (uintptr_t)out0 | (uintptr_t)ring0 | (uintptr_t)in1 | (uintptr_t)out1) & 15) return set_err(MIFFT_E_INVALID, "data buffers must be 16-byte aligned");
+    if (misaligned(15, {in0, out0, ring0, in1, out1})) return set_err(MIFFT_E_INVALID, "data buffers must be 16-byte aligned");
     if (ring0 == in0 || ring0 == out0) return set_err(MIFFT_E_INVALID, "fused pair: the ring must be a buffer of its own");
     if (grid < 1) return set_err(MIFFT_E_INVALID, "fused pair: grid >= 1");
     const long long batch = pz->outer;
@@ -1065,8 +1050,7 @@ int mifft_launch_fused_pair(const mifft_pass* passes, const void* in0, const voi
     int rc = fill_ctl(&f.c, sync, batch, lag, ring_slots, tiles0, tiles1, (hipStream_t)stream, "fused pair");
     if (rc) return rc;
     rc = mifft_fusedp(f64, split ? 1 : 0, nx, ny, nz, &f, (unsigned)grid, (hipStream_t)stream, 0, nullptr, nullptr, nullptr);
-    if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
-    return 0;
+    return hip_check((hipError_t)rc, "kernel launch");
 }
 
 int mifft_launch_chain_pipelined(const mifft_pass* passes, int32_t npasses, void* const bufs0[3], void* const bufs1[3],
@@ -1136,7 +1120,7 @@ int mifft_launch_chain_pipelined(const mifft_pass* passes, int32_t npasses, void
 }
 
 int mifft_nd_tiled_supported(int32_t precision, int32_t x, int32_t y, int32_t z) {
-    if (precision != MIFFT_F32 && precision != MIFFT_F64) return MIFFT_E_UNSUPPORTED;
+    if (bad_precision(precision)) return MIFFT_E_UNSUPPORTED;
     return mifft_nd2t(precision == MIFFT_F64, x, y, z, nullptr, nullptr, nullptr, 1) == 0 ? 0 : MIFFT_E_UNSUPPORTED;
 }
 
@@ -1144,7 +1128,7 @@ static int launch_nd_tiled(const mifft_pass* p, const mifft_tiling* t, const voi
                            mifft_stream_t stream) {
     if (!p || !t) return set_err(MIFFT_E_INVALID, "nd_tiled: null argument");
     if (p->kind != MIFFT_PASS_ND) return set_err(MIFFT_E_INVALID, "nd_tiled: not an ND pass");
-    if (p->precision != MIFFT_F32 && p->precision != MIFFT_F64) return set_err(MIFFT_E_INVALID, "bad precision %d", p->precision);
+    if (bad_precision(p->precision)) return set_err(MIFFT_E_INVALID, "bad precision %d", p->precision);
     if (p->layout != (split ? MIFFT_SPLIT : MIFFT_INTERLEAVED))
         return set_err(split ? MIFFT_E_INVALID : MIFFT_E_UNSUPPORTED, split ? "nd_tiled_split: the pass must say MIFFT_SPLIT" : "nd_tiled: interleaved data only (split planes: mifft_launch_nd_tiled_split)");
     if (mifft_nd_tiled_supported(p->precision, p->L, (int32_t)p->M, (int32_t)p->S) != 0)
@@ -1153,7 +1137,7 @@ static int launch_nd_tiled(const mifft_pass* p, const mifft_tiling* t, const voi
         t->parent_elems < t->pitch_z * p->S * t->cz || (t->pitch_y & 1) || (t->pitch_z & 1) || (t->parent_elems & 1))
         return set_err(MIFFT_E_INVALID, "nd_tiled: inconsistent tiling");
     if (!in0 || !out0 || (split && (!in1 || !out1))) return set_err(MIFFT_E_INVALID, "null data buffer");
-    if (((uintptr_t)in0 | (uintptr_t)out0 | (uintptr_t)in1 | (uintptr_t)out1) & 15) return set_err(MIFFT_E_INVALID, "data buffers must be 16-byte aligned");
+    if (misaligned(15, {in0, out0, in1, out1})) return set_err(MIFFT_E_INVALID, "data buffers must be 16-byte aligned");
     if ((p->L > 1 && !p->tw_L) || (p->M > 1 && !p->tw_lo) || (p->S > 1 && !p->tw_hi)) return set_err(MIFFT_E_INVALID, "ND pass: twiddle table missing");
     if (p->outer < 0) return set_err(MIFFT_E_INVALID, "negative outer count");
     if (p->outer == 0) return 0;
@@ -1167,10 +1151,7 @@ static int launch_nd_tiled(const mifft_pass* p, const mifft_tiling* t, const voi
     mifft::TiledGeom g;
     g.pitch_y = t->pitch_y; g.pitch_z = t->pitch_z; g.parent = t->parent_elems; g.tiles = p->outer;
     g.cx = t->cx; g.cy = t->cy; g.cz = t->cz;
-    const int rc = (split ? mifft_nd2t_split : mifft_nd2t)(p->precision == MIFFT_F64, p->L, (int)p->M, (int)p->S, &a, &g, (hipStream_t)stream, 0);
-    if (rc == -1) return set_err(MIFFT_E_INVALID, "grid too large");
-    if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
-    return 0;
+    return launched((split ? mifft_nd2t_split : mifft_nd2t)(p->precision == MIFFT_F64, p->L, (int)p->M, (int)p->S, &a, &g, (hipStream_t)stream, 0));
 }
 
 int mifft_launch_nd_tiled(const mifft_pass* p, const mifft_tiling* t, const void* in, void* out, mifft_stream_t stream) {
@@ -1184,37 +1165,35 @@ int mifft_launch_nd_tiled_split(const mifft_pass* p, const mifft_tiling* t, cons
 
 int mifft_aux_copy(const mifft_copy* c, const void* src0, const void* src1, void* dst0, void* dst1, mifft_stream_t stream) {
     if (!c || c->ndim < 1 || c->ndim > 6) return set_err(MIFFT_E_INVALID, "aux_copy: bad descriptor");
-    if (c->precision != MIFFT_F32 && c->precision != MIFFT_F64) return set_err(MIFFT_E_INVALID, "aux_copy: bad precision");
+    if (bad_precision(c->precision)) return set_err(MIFFT_E_INVALID, "aux_copy: bad precision");
     for (int d = 0; d < c->ndim; ++d)
         if (c->dims[d] < 1) return set_err(MIFFT_E_INVALID, "aux_copy: dims[%d] = %lld", d, (long long)c->dims[d]);
     if (!src0 || !dst0 || (c->src_split && !src1) || (c->dst_split && !dst1)) return set_err(MIFFT_E_INVALID, "aux_copy: null buffer");
     const int rc = mifft_aux_copy_launch(c, src0, src1, dst0, dst1, (hipStream_t)stream);
-    if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
-    return 0;
+    return hip_check((hipError_t)rc, "kernel launch");
 }
 
 int mifft_aux_mul_rows(int32_t precision, void* a, const void* b, int64_t rows, int64_t n, mifft_stream_t stream) {
     if (!a || !b || rows < 0 || n < 1) return set_err(MIFFT_E_INVALID, "aux_mul_rows: bad arguments");
     const int rc = mifft_aux_mul_rows_launch(precision == MIFFT_F64, a, b, rows, n, (hipStream_t)stream);
-    if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
-    return 0;
+    return hip_check((hipError_t)rc, "kernel launch");
 }
 
 int mifft_aux_count_mismatch(const void* a, const void* b, size_t nbytes, uint64_t* count, mifft_stream_t stream) {
     if (!a || !b || !count) return set_err(MIFFT_E_INVALID, "null argument");
-    if ((nbytes & 15) || (((uintptr_t)a | (uintptr_t)b) & 15) || ((uintptr_t)count & 7))
+    if ((nbytes & 15) || misaligned(15, {a, b}) || misaligned(7, {count}))
         return set_err(MIFFT_E_INVALID, "mifft_aux_count_mismatch: buffers and size in whole 16-byte words, an 8-byte aligned counter");
     const int rc = mifft_aux_mismatch_launch(a, b, (unsigned long long)(nbytes / 16), (unsigned long long*)count, (hipStream_t)stream);
-    return rc ? hip_check((hipError_t)rc, "kernel launch") : 0;
+    return hip_check((hipError_t)rc, "kernel launch");
 }
 
 int mifft_mixed_supported(int32_t precision, int32_t n) {
-    if (precision != MIFFT_F32 && precision != MIFFT_F64) return MIFFT_E_UNSUPPORTED;
+    if (bad_precision(precision)) return MIFFT_E_UNSUPPORTED;
     return mifft_mixed_supported_impl(precision == MIFFT_F64, n) == 0 ? 0 : MIFFT_E_UNSUPPORTED;
 }
 
 int mifft_mixed_radices(int32_t precision, int32_t n, int32_t* radix) {
-    if (precision != MIFFT_F32 && precision != MIFFT_F64) return MIFFT_E_UNSUPPORTED;
+    if (bad_precision(precision)) return MIFFT_E_UNSUPPORTED;
     if (!radix) return set_err(MIFFT_E_INVALID, "mixed radices: null result pointer");
     if (n < 2 || n > (1 << 24)) return MIFFT_E_UNSUPPORTED;
     const int ns = mifft_mixed_radices_impl(n, radix);
@@ -1233,14 +1212,9 @@ int mifft_launch_mixed_rows(int32_t precision, int32_t n, int64_t rows, int64_t 
     if (stride_in == n && stride_out == n && g_debug[MIFFT_DEBUG_ROWS_ND] != 1 && mifft_mixed_nd_rows_ok_impl(precision == MIFFT_F64, n) == 0 &&
         (g_debug[MIFFT_DEBUG_ROWS_ND] == 2 || mixed_rows_prefer_nd(precision == MIFFT_F64, n))) {
         const int rcn = mifft_mixed_nd_launch(precision == MIFFT_F64, n, 1, 1, rows, in, out, tw, nullptr, nullptr, inverse ? 3 : 0, scale, (hipStream_t)stream);
-        if (rcn == -1) return set_err(MIFFT_E_INVALID, "grid too large");
-        if (rcn != 0 && rcn != -2) return hip_check((hipError_t)rcn, "kernel launch");
-        if (rcn == 0) return 0;
+        if (rcn != -2) return launched(rcn);
     }
-    const int rc = mifft_mixed_launch(precision == MIFFT_F64, n, rows, stride_in, stride_out, 1, in, out, tw, inverse ? 3 : 0, scale, (hipStream_t)stream);
-    if (rc == -1) return set_err(MIFFT_E_INVALID, "grid too large");
-    if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
-    return 0;
+    return launched(mifft_mixed_launch(precision == MIFFT_F64, n, rows, stride_in, stride_out, 1, in, out, tw, inverse ? 3 : 0, scale, (hipStream_t)stream));
 }
 
 int mifft_launch_mixed_lines(int32_t precision, int32_t n, int64_t outer, int64_t inner, const void* in, void* out, const void* tw,
@@ -1248,19 +1222,16 @@ int mifft_launch_mixed_lines(int32_t precision, int32_t n, int64_t outer, int64_
     if (mifft_mixed_supported(precision, n) != 0) return set_err(MIFFT_E_UNSUPPORTED, "mixed lines: no kernel for n = %d", n);
     if (!in || !out || !tw) return set_err(MIFFT_E_INVALID, "mixed lines: null buffer");
     if (outer < 0 || inner < 1) return set_err(MIFFT_E_INVALID, "mixed lines: bad index space");
-    if (mul3_checked(outer, inner, (long long)n * (precision == MIFFT_F64 ? 16 : 8)) < 0)
+    if (mul3_checked(outer, inner, (long long)n * complex_bytes(precision)) < 0)
         return set_err(MIFFT_E_INVALID, "mixed lines: outer * inner * n overflows");
     if (const char* why = check_rows(precision, in, out, 0, n, n, n)) return set_err(MIFFT_E_INVALID, "mixed lines: %s", why);
     if (outer == 0) return 0;
     const int flags = (conj_in ? 1 : 0) | (conj_out ? 2 : 0);
-    const int rc = mifft_mixed_launch(precision == MIFFT_F64, n, outer * inner, n, n, inner, in, out, tw, flags, scale, (hipStream_t)stream);
-    if (rc == -1) return set_err(MIFFT_E_INVALID, "grid too large");
-    if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
-    return 0;
+    return launched(mifft_mixed_launch(precision == MIFFT_F64, n, outer * inner, n, n, inner, in, out, tw, flags, scale, (hipStream_t)stream));
 }
 
 int mifft_mixed_long_split(int32_t precision, int64_t n, int32_t* n1, int32_t* n2) {
-    if (precision != MIFFT_F32 && precision != MIFFT_F64) return MIFFT_E_UNSUPPORTED;
+    if (bad_precision(precision)) return MIFFT_E_UNSUPPORTED;
     if (!n1 || !n2) return set_err(MIFFT_E_INVALID, "mixed long: null result pointer");
     int a = 0, b = 0;
     if (mifft_mixed_long_split_impl(precision == MIFFT_F64, n, &a, &b) != 0) return MIFFT_E_UNSUPPORTED;
@@ -1277,21 +1248,15 @@ int mifft_launch_mixed_long(int32_t precision, int32_t n1, int32_t n2, int64_t b
     if (mid == in) return set_err(MIFFT_E_INVALID, "mixed long: the first pass transposes, `mid` must not be the input");
     if (batch < 0 || tw_shift < 1 || tw_shift > 23) return set_err(MIFFT_E_INVALID, "mixed long: bad batch / table shift");
     if ((long long)n1 * n2 > (1ll << 24)) return set_err(MIFFT_E_INVALID, "mixed long: n1 * n2 = %lld exceeds 2^24", (long long)n1 * n2);
-    if (mul3_checked(batch, (long long)n1 * n2, precision == MIFFT_F64 ? 16 : 8) < 0) return set_err(MIFFT_E_INVALID, "mixed long: batch * n overflows");
-    {
-        const uintptr_t mask = precision == MIFFT_F64 ? 15 : 7;
-        if (((uintptr_t)in | (uintptr_t)mid | (uintptr_t)out) & mask) return set_err(MIFFT_E_INVALID, "mixed long: data buffers must be aligned to one complex number");
-    }
+    if (mul3_checked(batch, (long long)n1 * n2, complex_bytes(precision)) < 0) return set_err(MIFFT_E_INVALID, "mixed long: batch * n overflows");
+    if (misaligned_complex(precision, {in, mid, out})) return set_err(MIFFT_E_INVALID, "mixed long: data buffers must be aligned to one complex number");
     if (batch == 0) return 0;
-    const int rc = mifft_mixed_long_launch(precision == MIFFT_F64, n1, n2, batch, in, mid, out, tw1, tw2, tw_lo, tw_hi, tw_shift,
-                                           inverse ? 3 : 0, scale, (hipStream_t)stream);
-    if (rc == -1) return set_err(MIFFT_E_INVALID, "grid too large");
-    if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
-    return 0;
+    return launched(mifft_mixed_long_launch(precision == MIFFT_F64, n1, n2, batch, in, mid, out, tw1, tw2, tw_lo, tw_hi, tw_shift,
+                                           inverse ? 3 : 0, scale, (hipStream_t)stream));
 }
 
 int mifft_bluestein_padded(int32_t precision, int32_t n, int32_t* m) {
-    if (precision != MIFFT_F32 && precision != MIFFT_F64) return MIFFT_E_UNSUPPORTED;
+    if (bad_precision(precision)) return MIFFT_E_UNSUPPORTED;
     if (!m) return set_err(MIFFT_E_INVALID, "bluestein: null result pointer");
     const int v = mifft_bluestein_padded_impl(precision == MIFFT_F64, n);
     if (v <= 0) return MIFFT_E_UNSUPPORTED;
@@ -1302,7 +1267,7 @@ int mifft_bluestein_padded(int32_t precision, int32_t n, int32_t* m) {
 int mifft_launch_bluestein_rows(int32_t precision, int32_t n, int32_t m, int64_t rows, int64_t stride_in, int64_t stride_out, const void* in,
                                 void* out, const void* tw, const void* chirp, const void* bhat, int32_t inverse, double scale,
                                 mifft_stream_t stream) {
-    if (precision != MIFFT_F32 && precision != MIFFT_F64) return MIFFT_E_UNSUPPORTED;
+    if (bad_precision(precision)) return MIFFT_E_UNSUPPORTED;
     if (n < 2 || m < 2 * (int64_t)n - 1 || mifft_bluestein_len_supported_impl(precision == MIFFT_F64, m) != 0)
         return set_err(MIFFT_E_UNSUPPORTED, "bluestein rows: no kernel for n = %d padded to %d", n, m);
     if (!in || !out || !tw || !chirp || !bhat) return set_err(MIFFT_E_INVALID, "bluestein rows: null buffer");
@@ -1312,13 +1277,11 @@ int mifft_launch_bluestein_rows(int32_t precision, int32_t n, int32_t m, int64_t
     const int rc = mifft_bluestein_launch(precision == MIFFT_F64, n, m, rows, stride_in, stride_out, in, out, tw, chirp, bhat,
                                           inverse ? 3 : 0, scale, (hipStream_t)stream);
     if (rc == -2) return set_err(MIFFT_E_UNSUPPORTED, "bluestein rows: no kernel for n = %d padded to %d", n, m);
-    if (rc == -1) return set_err(MIFFT_E_INVALID, "grid too large");
-    if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
-    return 0;
+    return launched(rc);
 }
 
 int mifft_mixed_nd_supported(int32_t precision, int32_t x, int32_t y, int32_t z) {
-    if (precision != MIFFT_F32 && precision != MIFFT_F64) return MIFFT_E_UNSUPPORTED;
+    if (bad_precision(precision)) return MIFFT_E_UNSUPPORTED;
     return mifft_mixed_nd_supported_impl(precision == MIFFT_F64, x, y, z) == 0 ? 0 : MIFFT_E_UNSUPPORTED;
 }
 
@@ -1327,7 +1290,7 @@ int mifft_launch_mixed_nd(int32_t precision, int32_t x, int32_t y, int32_t z, in
     if (mifft_mixed_nd_supported(precision, x, y, z) != 0) return set_err(MIFFT_E_UNSUPPORTED, "mixed nd: no kernel for %d x %d x %d", z, y, x);
     if (!in || !out || (x > 1 && !tw_x) || (y > 1 && !tw_y) || (z > 1 && !tw_z)) return set_err(MIFFT_E_INVALID, "mixed nd: null buffer");
     if (const char* why = check_rows(precision, in, out, 0, 0, 0, 0)) return set_err(MIFFT_E_INVALID, "mixed nd: %s", why);
-    if (transforms < 0 || mul3_checked(transforms, (long long)x * y * z, precision == MIFFT_F64 ? 16 : 8) < 0)
+    if (transforms < 0 || mul3_checked(transforms, (long long)x * y * z, complex_bytes(precision)) < 0)
         return set_err(MIFFT_E_INVALID, "mixed nd: bad transform count");
     if (transforms == 0) return 0;
     // inverse: 0 forward, 1 inverse = conjugate on load and on store; 2 / 4: on load / on store only (one end of a composition)
@@ -1335,14 +1298,12 @@ int mifft_launch_mixed_nd(int32_t precision, int32_t x, int32_t y, int32_t z, in
     if (inverse != 0 && inverse != 1 && inverse != 2 && inverse != 4) return set_err(MIFFT_E_INVALID, "mixed nd: inverse must be 0, 1, 2 or 4");
     const int rc = mifft_mixed_nd_launch(precision == MIFFT_F64, x, y, z, transforms, in, out, tw_x, tw_y, tw_z, flags, scale, (hipStream_t)stream);
     if (rc == -2) return set_err(MIFFT_E_UNSUPPORTED, "mixed nd: no kernel for %d x %d x %d", z, y, x);
-    if (rc == -1) return set_err(MIFFT_E_INVALID, "grid too large");
-    if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
-    return 0;
+    return launched(rc);
 }
 
 int mifft_launch_real_post(const mifft_real_post* d, mifft_stream_t stream) {
     if (!d) return set_err(MIFFT_E_INVALID, "real post: null descriptor");
-    if (d->precision != MIFFT_F32 && d->precision != MIFFT_F64) return set_err(MIFFT_E_INVALID, "real post: bad precision %d", d->precision);
+    if (bad_precision(d->precision)) return set_err(MIFFT_E_INVALID, "real post: bad precision %d", d->precision);
     if (d->inverse != 0 && d->inverse != 1) return set_err(MIFFT_E_INVALID, "real post: inverse must be 0 or 1");
     if (d->nx < 2 || !is_pow2(d->nx) || !is_pow2(d->ny) || !is_pow2(d->nz))
         return set_err(MIFFT_E_INVALID, "real post: shape %d x %d x %d is not powers of two with nx >= 2", d->nz, d->ny, d->nx);
@@ -1352,44 +1313,38 @@ int mifft_launch_real_post(const mifft_real_post* d, mifft_stream_t stream) {
     const long long L = d->nx / 2, rows = (long long)d->ny * d->nz;
     const long long n_in = rows * (d->inverse ? L + 1 : L), n_out = rows * (d->inverse ? L : L + 1);
     if (d->stride_in < n_in || d->stride_out < n_out) return set_err(MIFFT_E_INVALID, "real post: item pitch below the item's size");
-    const long long esz = d->precision == MIFFT_F64 ? 16 : 8;
-    if (((uintptr_t)d->in | (uintptr_t)d->out | (uintptr_t)d->tw) & (uintptr_t)(esz - 1))
+    const long long esz = complex_bytes(d->precision);
+    if (misaligned_complex(d->precision, {d->in, d->out, d->tw}))
         return set_err(MIFFT_E_INVALID, "real post: buffers must be aligned to one complex number");
     if (mul3_checked(d->outer, d->stride_in, esz) < 0 || mul3_checked(d->outer, d->stride_out, esz) < 0)
         return set_err(MIFFT_E_INVALID, "real post: items * pitch overflows");
     if (d->outer == 0) return 0;
-    const uintptr_t i0 = (uintptr_t)d->in, i1 = i0 + (uintptr_t)(((d->outer - 1) * d->stride_in + n_in) * esz);
-    const uintptr_t o0 = (uintptr_t)d->out, o1 = o0 + (uintptr_t)(((d->outer - 1) * d->stride_out + n_out) * esz);
-    if (i0 < o1 && o0 < i1) return set_err(MIFFT_E_INVALID, "real post: input and output overlap (out of place only)");
-    const int rc = mifft_real_post_launch(d->precision == MIFFT_F64, d->inverse, d->nx, d->ny, d->nz, d->outer, d->stride_in, d->stride_out,
-                                          d->in, d->out, d->tw, d->scale, (hipStream_t)stream);
-    if (rc == -1) return set_err(MIFFT_E_INVALID, "grid too large");
-    if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
-    return 0;
+    if (overlap(d->in, (uintptr_t)(((d->outer - 1) * d->stride_in + n_in) * esz), d->out, (uintptr_t)(((d->outer - 1) * d->stride_out + n_out) * esz)))
+        return set_err(MIFFT_E_INVALID, "real post: input and output overlap (out of place only)");
+    return launched(mifft_real_post_launch(d->precision == MIFFT_F64, d->inverse, d->nx, d->ny, d->nz, d->outer, d->stride_in, d->stride_out,
+                                          d->in, d->out, d->tw, d->scale, (hipStream_t)stream));
 }
 int mifft_real_row_supported(int32_t precision, int32_t n) {
-    if ((precision != MIFFT_F32 && precision != MIFFT_F64) || n < 4 || !is_pow2(n)) return MIFFT_E_UNSUPPORTED;
+    if (bad_precision(precision) || n < 4 || !is_pow2(n)) return MIFFT_E_UNSUPPORTED;
     const int rc = precision == MIFFT_F64 ? mifft_real_row_dispatch_f64(n / 2, 0, nullptr, nullptr, 1)
                                           : mifft_real_row_dispatch_f32(n / 2, 0, nullptr, nullptr, 1);
     return rc == 0 ? 0 : MIFFT_E_UNSUPPORTED;
 }
 int mifft_launch_real_row(int32_t precision, int32_t n, int32_t inverse, int64_t rows, const void* in, void* out, const void* tw_half,
                           const void* tw_sep, double scale, mifft_stream_t stream) {
-    if (precision != MIFFT_F32 && precision != MIFFT_F64) return set_err(MIFFT_E_INVALID, "real row: bad precision %d", precision);
+    if (bad_precision(precision)) return set_err(MIFFT_E_INVALID, "real row: bad precision %d", precision);
     if (n < 2 || !is_pow2(n)) return set_err(MIFFT_E_INVALID, "real row: n = %d is not a power of two >= 2", n);
     if (mifft_real_row_supported(precision, n) != 0) return set_err(MIFFT_E_UNSUPPORTED, "real row: no kernel for n = %d", n);
     if (inverse != 0 && inverse != 1) return set_err(MIFFT_E_INVALID, "real row: inverse must be 0 or 1");
     if (rows < 0) return set_err(MIFFT_E_INVALID, "real row: negative row count");
     if (!in || !out || !tw_half || !tw_sep) return set_err(MIFFT_E_INVALID, "real row: null buffer");
-    const long long esz = precision == MIFFT_F64 ? 16 : 8;
-    if (((uintptr_t)in | (uintptr_t)out | (uintptr_t)tw_half | (uintptr_t)tw_sep) & (uintptr_t)(esz - 1))
+    const long long esz = complex_bytes(precision);
+    if (misaligned_complex(precision, {in, out, tw_half, tw_sep}))
         return set_err(MIFFT_E_INVALID, "real row: buffers must be aligned to one complex number");
     const long long L = n / 2, n_in = inverse ? L + 1 : L, n_out = inverse ? L : L + 1;
     if (mul3_checked(rows, n_in + n_out, esz) < 0) return set_err(MIFFT_E_INVALID, "real row: rows * n overflows");
     if (rows == 0) return 0;
-    const uintptr_t i0 = (uintptr_t)in, i1 = i0 + (uintptr_t)(rows * n_in * esz);
-    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (uintptr_t)(rows * n_out * esz);
-    if (i0 < o1 && o0 < i1) return set_err(MIFFT_E_INVALID, "real row: input and output overlap (out of place only)");
+    if (overlap(in, (uintptr_t)(rows * n_in * esz), out, (uintptr_t)(rows * n_out * esz))) return set_err(MIFFT_E_INVALID, "real row: input and output overlap (out of place only)");
     mifft::TileArgs a = {};
     a.in0 = in;
     a.out0 = out;
@@ -1401,13 +1356,11 @@ int mifft_launch_real_row(int32_t precision, int32_t n, int32_t inverse, int64_t
     const int rc = precision == MIFFT_F64 ? mifft_real_row_dispatch_f64((int)L, inverse, &a, (hipStream_t)stream, 0)
                                           : mifft_real_row_dispatch_f32((int)L, inverse, &a, (hipStream_t)stream, 0);
     if (rc == -2) return set_err(MIFFT_E_UNSUPPORTED, "real row: no kernel for n = %d", n);
-    if (rc == -1) return set_err(MIFFT_E_INVALID, "grid too large");
-    if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
-    return 0;
+    return launched(rc);
 }
 // convolution rows (fft_conv_row.hpp): complex rows of n points (L = n), real rows of n reals (L = n / 2 packed points)
 int mifft_conv_row_supported(int32_t precision, int32_t real, int32_t n) {
-    if ((precision != MIFFT_F32 && precision != MIFFT_F64) || (real != 0 && real != 1) || n < 2 || !is_pow2(n)) return MIFFT_E_UNSUPPORTED;
+    if (bad_precision(precision) || (real != 0 && real != 1) || n < 2 || !is_pow2(n)) return MIFFT_E_UNSUPPORTED;
     if (real && n < 4) return MIFFT_E_UNSUPPORTED;
     const int L = real ? n / 2 : n;
     const int rc = precision == MIFFT_F64 ? mifft_conv_row_dispatch_f64(real, L, nullptr, nullptr, 1)
@@ -1416,15 +1369,15 @@ int mifft_conv_row_supported(int32_t precision, int32_t real, int32_t n) {
 }
 int mifft_launch_conv_row(int32_t precision, int32_t real, int32_t n, int64_t rows, const void* in, void* out, const void* spectrum,
                           int64_t spectrum_pitch, int32_t correlate, const void* tw, const void* tw_sep, double scale, mifft_stream_t stream) {
-    if (precision != MIFFT_F32 && precision != MIFFT_F64) return set_err(MIFFT_E_INVALID, "conv row: bad precision %d", precision);
+    if (bad_precision(precision)) return set_err(MIFFT_E_INVALID, "conv row: bad precision %d", precision);
     if (real != 0 && real != 1) return set_err(MIFFT_E_INVALID, "conv row: real must be 0 or 1");
     if (n < 2 || !is_pow2(n)) return set_err(MIFFT_E_INVALID, "conv row: n = %d is not a power of two >= 2", n);
     if (mifft_conv_row_supported(precision, real, n) != 0) return set_err(MIFFT_E_UNSUPPORTED, "conv row: no kernel for n = %d", n);
     if (correlate != 0 && correlate != 1) return set_err(MIFFT_E_INVALID, "conv row: correlate must be 0 or 1");
     if (rows < 0) return set_err(MIFFT_E_INVALID, "conv row: negative row count");
     if (!in || !out || !spectrum || !tw || (real && !tw_sep)) return set_err(MIFFT_E_INVALID, "conv row: null buffer");
-    const long long esz = precision == MIFFT_F64 ? 16 : 8;
-    if (((uintptr_t)in | (uintptr_t)out | (uintptr_t)spectrum | (uintptr_t)tw | (uintptr_t)tw_sep) & (uintptr_t)(esz - 1))
+    const long long esz = complex_bytes(precision);
+    if (misaligned_complex(precision, {in, out, spectrum, tw, tw_sep}))
         return set_err(MIFFT_E_INVALID, "conv row: buffers must be aligned to one complex number");
     const long long L = real ? n / 2 : n, sp = real ? L + 1 : L;
     if (spectrum_pitch != 0 && spectrum_pitch < sp)
@@ -1432,12 +1385,9 @@ int mifft_launch_conv_row(int32_t precision, int32_t real, int32_t n, int64_t ro
     if (mul3_checked(rows, L, esz) < 0 || mul3_checked(rows, spectrum_pitch > sp ? spectrum_pitch : sp, esz) < 0)
         return set_err(MIFFT_E_INVALID, "conv row: rows * n overflows");
     if (rows == 0) return 0;
-    const uintptr_t i0 = (uintptr_t)in, i1 = i0 + (uintptr_t)(rows * L * esz);
-    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (uintptr_t)(rows * L * esz);
-    if (i0 != o0 && i0 < o1 && o0 < i1) return set_err(MIFFT_E_INVALID, "conv row: input and output overlap without being equal");
-    const uintptr_t s0 = (uintptr_t)spectrum,
-                    s1 = s0 + (uintptr_t)(((spectrum_pitch ? (rows - 1) * spectrum_pitch : 0) + sp) * esz);
-    if ((s0 < i1 && i0 < s1) || (s0 < o1 && o0 < s1)) return set_err(MIFFT_E_INVALID, "conv row: the spectrum overlaps the data");
+    const uintptr_t bytes = (uintptr_t)(rows * L * esz), sbytes = (uintptr_t)(((spectrum_pitch ? (rows - 1) * spectrum_pitch : 0) + sp) * esz);
+    if (in != out && overlap(in, bytes, out, bytes)) return set_err(MIFFT_E_INVALID, "conv row: input and output overlap without being equal");
+    if (overlap(spectrum, sbytes, in, bytes) || overlap(spectrum, sbytes, out, bytes)) return set_err(MIFFT_E_INVALID, "conv row: the spectrum overlaps the data");
     mifft::ConvRowArgs a = {};
     a.in = in;
     a.out = out;
@@ -1451,31 +1401,25 @@ int mifft_launch_conv_row(int32_t precision, int32_t real, int32_t n, int64_t ro
     const int rc = precision == MIFFT_F64 ? mifft_conv_row_dispatch_f64(real, (int)L, &a, (hipStream_t)stream, 0)
                                           : mifft_conv_row_dispatch_f32(real, (int)L, &a, (hipStream_t)stream, 0);
     if (rc == -2) return set_err(MIFFT_E_UNSUPPORTED, "conv row: no kernel for n = %d", n);
-    if (rc == -1) return set_err(MIFFT_E_INVALID, "grid too large");
-    if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
-    return 0;
+    return launched(rc);
 }
 int mifft_aux_mul_spectrum(int32_t precision, void* data, const void* spectrum, int64_t items, int64_t points, int64_t spectrum_pitch,
                            int32_t correlate, double scale, mifft_stream_t stream) {
-    if (precision != MIFFT_F32 && precision != MIFFT_F64) return set_err(MIFFT_E_INVALID, "mul_spectrum: bad precision %d", precision);
+    if (bad_precision(precision)) return set_err(MIFFT_E_INVALID, "mul_spectrum: bad precision %d", precision);
     if (!data || !spectrum) return set_err(MIFFT_E_INVALID, "mul_spectrum: null buffer");
     if (items < 0 || points < 1 || (spectrum_pitch != 0 && spectrum_pitch < points) || (correlate != 0 && correlate != 1))
         return set_err(MIFFT_E_INVALID, "mul_spectrum: bad arguments");
-    const long long esz = precision == MIFFT_F64 ? 16 : 8;
-    if (((uintptr_t)data | (uintptr_t)spectrum) & (uintptr_t)(esz - 1))
+    if (misaligned_complex(precision, {data, spectrum}))
         return set_err(MIFFT_E_INVALID, "mul_spectrum: buffers must be aligned to one complex number");
-    if (mul3_checked(items, points, esz) < 0) return set_err(MIFFT_E_INVALID, "mul_spectrum: items * points overflows");
-    const int rc = mifft_aux_mul_spectrum_launch(precision == MIFFT_F64, data, spectrum, items, points, spectrum_pitch, correlate, scale,
-                                                 (hipStream_t)stream);
-    if (rc == -1) return set_err(MIFFT_E_INVALID, "grid too large");
-    if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
-    return 0;
+    if (mul3_checked(items, points, complex_bytes(precision)) < 0) return set_err(MIFFT_E_INVALID, "mul_spectrum: items * points overflows");
+    return launched(mifft_aux_mul_spectrum_launch(precision == MIFFT_F64, data, spectrum, items, points, spectrum_pitch, correlate, scale,
+                                                 (hipStream_t)stream));
 }
 // cosine and sine transforms (fft_r2r.hip): the steps around the complex transform of the packed data
 static int r2r_step(const mifft_r2r_step* d, int post, mifft_stream_t stream) {
     const char* what = post ? "r2r post" : "r2r pre";
     if (!d) return set_err(MIFFT_E_INVALID, "%s: null descriptor", what);
-    if (d->precision != MIFFT_F32 && d->precision != MIFFT_F64) return set_err(MIFFT_E_INVALID, "%s: bad precision %d", what, d->precision);
+    if (bad_precision(d->precision)) return set_err(MIFFT_E_INVALID, "%s: bad precision %d", what, d->precision);
     if (d->inverse != 0 && d->inverse != 1) return set_err(MIFFT_E_INVALID, "%s: inverse must be 0 or 1", what);
     if (d->kind != 0 && d->kind != 1) return set_err(MIFFT_E_INVALID, "%s: kind must be 0 (DCT) or 1 (DST)", what);
     if (d->ndim < 1 || d->ndim > 3) return set_err(MIFFT_E_INVALID, "%s: ndim must be 1, 2 or 3", what);
@@ -1491,33 +1435,30 @@ static int r2r_step(const mifft_r2r_step* d, int post, mifft_stream_t stream) {
     if (d->outer < 0) return set_err(MIFFT_E_INVALID, "%s: negative item count", what);
     if (!d->in || !d->out || (!perm && !d->tw)) return set_err(MIFFT_E_INVALID, "%s: null buffer", what);
     const long long rsz = d->precision == MIFFT_F64 ? 8 : 4;
-    const uintptr_t cmask = (uintptr_t)(2 * rsz - 1), rmask = (uintptr_t)(rsz - 1);
     // the packed side (v, Z, Z') is whole complex numbers; the user side real numbers
-    const uintptr_t packed = (uintptr_t)(perm ? (d->inverse ? d->in : d->out) : (d->inverse ? d->out : d->in));
-    if ((((uintptr_t)d->in | (uintptr_t)d->out) & rmask) || (!single && (packed & cmask)) || (!perm && ((uintptr_t)d->tw & cmask)))
+    const void* packed = perm ? (d->inverse ? d->in : d->out) : (d->inverse ? d->out : d->in);
+    if (misaligned((uintptr_t)rsz - 1, {d->in, d->out}) || (!single && misaligned_complex(d->precision, {packed})) ||
+        (!perm && misaligned_complex(d->precision, {d->tw})))
         return set_err(MIFFT_E_INVALID, "%s: buffers must be aligned to one real (packed side: one complex) number", what);
     if (mul3_checked(d->outer, pts, rsz) < 0) return set_err(MIFFT_E_INVALID, "%s: items * points overflows", what);
     if (d->outer == 0) return 0;
-    const uintptr_t i0 = (uintptr_t)d->in, o0 = (uintptr_t)d->out, bytes = (uintptr_t)(d->outer * pts * rsz);
-    if (!(single && i0 == o0) && i0 < o0 + bytes && o0 < i0 + bytes)
+    const uintptr_t bytes = (uintptr_t)(d->outer * pts * rsz);
+    if (!(single && d->in == d->out) && overlap(d->in, bytes, d->out, bytes))
         return set_err(MIFFT_E_INVALID, "%s: input and output overlap (out of place only)", what);
     const int n[3] = {d->n[0], d->n[1], d->n[2]};
-    const int rc = mifft_r2r_step_launch(d->precision == MIFFT_F64, post, d->inverse, d->kind, d->ndim, n, d->outer, d->in, d->out, d->tw,
-                                         d->scale, (hipStream_t)stream);
-    if (rc == -1) return set_err(MIFFT_E_INVALID, "grid too large");
-    if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
-    return 0;
+    return launched(mifft_r2r_step_launch(d->precision == MIFFT_F64, post, d->inverse, d->kind, d->ndim, n, d->outer, d->in, d->out, d->tw,
+                                         d->scale, (hipStream_t)stream));
 }
 // one-launch cosine / sine rows (fft_r2r_row.hpp): rows of n reals, L = n / 2 packed points
 int mifft_r2r_row_supported(int32_t precision, int32_t n) {
-    if ((precision != MIFFT_F32 && precision != MIFFT_F64) || n < 4 || !is_pow2(n)) return MIFFT_E_UNSUPPORTED;
+    if (bad_precision(precision) || n < 4 || !is_pow2(n)) return MIFFT_E_UNSUPPORTED;
     const int rc = precision == MIFFT_F64 ? mifft_r2r_row_dispatch_f64(n / 2, 0, nullptr, nullptr, 1)
                                           : mifft_r2r_row_dispatch_f32(n / 2, 0, nullptr, nullptr, 1);
     return rc == 0 ? 0 : MIFFT_E_UNSUPPORTED;
 }
 int mifft_launch_r2r_row(int32_t precision, int32_t n, int32_t inverse, int32_t kind, int64_t rows, const void* in, void* out,
                          const void* tw_stage, const void* tw_sep, const void* tab, mifft_stream_t stream) {
-    if (precision != MIFFT_F32 && precision != MIFFT_F64) return set_err(MIFFT_E_INVALID, "r2r row: bad precision %d", precision);
+    if (bad_precision(precision)) return set_err(MIFFT_E_INVALID, "r2r row: bad precision %d", precision);
     if (n < 4 || !is_pow2(n)) return set_err(MIFFT_E_INVALID, "r2r row: n = %d is not a power of two >= 4", n);
     if (mifft_r2r_row_supported(precision, n) != 0) return set_err(MIFFT_E_UNSUPPORTED, "r2r row: no kernel for n = %d", n);
     if (inverse != 0 && inverse != 1) return set_err(MIFFT_E_INVALID, "r2r row: inverse must be 0 or 1");
@@ -1525,12 +1466,12 @@ int mifft_launch_r2r_row(int32_t precision, int32_t n, int32_t inverse, int32_t 
     if (rows < 0) return set_err(MIFFT_E_INVALID, "r2r row: negative row count");
     if (!in || !out || !tw_stage || !tw_sep || !tab) return set_err(MIFFT_E_INVALID, "r2r row: null buffer");
     const long long rsz = precision == MIFFT_F64 ? 8 : 4;
-    if ((((uintptr_t)in | (uintptr_t)out) & 15) || (((uintptr_t)tw_stage | (uintptr_t)tw_sep | (uintptr_t)tab) & (uintptr_t)(2 * rsz - 1)))
+    if (misaligned(15, {in, out}) || misaligned_complex(precision, {tw_stage, tw_sep, tab}))
         return set_err(MIFFT_E_INVALID, "r2r row: data must be 16-byte aligned, tables aligned to one complex number");
     if (mul3_checked(rows, n, rsz) < 0) return set_err(MIFFT_E_INVALID, "r2r row: rows * n overflows");
     if (rows == 0) return 0;
-    const uintptr_t i0 = (uintptr_t)in, o0 = (uintptr_t)out, bytes = (uintptr_t)(rows * n * rsz);
-    if (i0 != o0 && i0 < o0 + bytes && o0 < i0 + bytes)
+    const uintptr_t bytes = (uintptr_t)(rows * n * rsz);
+    if (in != out && overlap(in, bytes, out, bytes))
         return set_err(MIFFT_E_INVALID, "r2r row: input and output overlap without being the same buffer");
     mifft::TileArgs a = {};
     a.in0 = in;
@@ -1545,9 +1486,7 @@ int mifft_launch_r2r_row(int32_t precision, int32_t n, int32_t inverse, int32_t 
     const int rc = precision == MIFFT_F64 ? mifft_r2r_row_dispatch_f64(n / 2, inverse, &a, (hipStream_t)stream, 0)
                                           : mifft_r2r_row_dispatch_f32(n / 2, inverse, &a, (hipStream_t)stream, 0);
     if (rc == -2) return set_err(MIFFT_E_UNSUPPORTED, "r2r row: no kernel for n = %d", n);
-    if (rc == -1) return set_err(MIFFT_E_INVALID, "grid too large");
-    if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
-    return 0;
+    return launched(rc);
 }
 int mifft_launch_r2r_pre(const mifft_r2r_step* desc, mifft_stream_t stream) { return r2r_step(desc, 0, stream); }
 int mifft_launch_r2r_post(const mifft_r2r_step* desc, mifft_stream_t stream) { return r2r_step(desc, 1, stream); }
@@ -1591,14 +1530,13 @@ int mifft_launch_half(int32_t x, int32_t y, int32_t z, int32_t variant, int32_t 
             d[nd] = dims_in[ax];
             tw[nd++] = tw_in[ax];
         }
-    if (((uintptr_t)in | (uintptr_t)out) & 15) return set_err(MIFFT_E_INVALID, "half: buffers must be 16-byte aligned");
-    if (((uintptr_t)tw[0] | (uintptr_t)tw[1] | (uintptr_t)tw[2]) & 7) return set_err(MIFFT_E_INVALID, "half: tables must be 8-byte aligned");
+    if (misaligned(15, {in, out})) return set_err(MIFFT_E_INVALID, "half: buffers must be 16-byte aligned");
+    if (misaligned(7, {tw[0], tw[1], tw[2]})) return set_err(MIFFT_E_INVALID, "half: tables must be 8-byte aligned");
     const long long n = d[0] * d[1] * d[2];
     if (mul3_checked(transforms, n, 4) < 0) return set_err(MIFFT_E_INVALID, "half: transforms * points overflows");
     if (transforms == 0) return 0;
     const uintptr_t bytes = (uintptr_t)(transforms * n * 4);
-    const uintptr_t i0 = (uintptr_t)in, o0 = (uintptr_t)out;
-    if (i0 != o0 && i0 < o0 + bytes && o0 < i0 + bytes)
+    if (in != out && overlap(in, bytes, out, bytes))
         return set_err(MIFFT_E_INVALID, "half: input and output overlap (in place is exact aliasing only)");
     hipStream_t s = (hipStream_t)stream;
     int rc;
@@ -1608,12 +1546,10 @@ int mifft_launch_half(int32_t x, int32_t y, int32_t z, int32_t variant, int32_t 
         a.in0 = in; a.out0 = out;
         a.tw[0] = tw[0]; a.tw[1] = tw[1]; a.tw[2] = tw[2];
         a.total = transforms * n;
+        // (with the register edge of the fp32 twin: the last stage writes runs of >= 16 points straight to HBM)
         if (nd_stage_list(d, false, &a) != 0) return set_err(MIFFT_E_UNSUPPORTED, "half: too many stages");
         a.inverse = inverse;
         a.scale = scale;
-        // the register edge of the fp32 twin (launch_nd): the last stage writes runs of >= 16 points straight to HBM
-        const int axn = a.st_axis[a.nstages - 1];
-        a.edge_out = (((d[axn] / a.st_radix[a.nstages - 1]) << a.logS[axn]) * 8 >= 128) ? 1 : 0;
         rc = mifft_c32_nd_launch(n, &a, s);
     } else {
         mifft::TileArgs a;
@@ -1632,9 +1568,7 @@ int mifft_launch_half(int32_t x, int32_t y, int32_t z, int32_t variant, int32_t 
         }
     }
     if (rc == -2) return set_err(MIFFT_E_UNSUPPORTED, "half: no kernel for %d x %d x %d", z, y, x);
-    if (rc == -1) return set_err(MIFFT_E_INVALID, "grid too large");
-    if (rc != 0) return hip_check((hipError_t)rc, "kernel launch");
-    return 0;
+    return launched(rc);
 }
 int mifft_time_chain(const mifft_pass* passes, int32_t npasses, void* const bufs0[3], void* const bufs1[3], mifft_stream_t stream,
                      int32_t repeats, float* ms_total) {

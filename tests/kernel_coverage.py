@@ -70,69 +70,68 @@ def fixed_nd_shapes(prec):
     return _tables["fixed"][prec]
 
 
-def nd2z_shapes(prec):
-    """(x, y, z) with a several-work-groups-per-transform instance, read off the instantiation tables csrc/fft_nd2z_<prec>.hip"""
-    if "nd2z" not in _tables:
-        import os
-        import re
-        out = {}
-        for name, ctype in (("f32", "float"), ("f64", "double")):
-            path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "pyfft_amd", "csrc", "fft_nd2z_%s.hip" % name)
-            text = "\n".join(l for l in open(path).read().splitlines() if not l.lstrip().startswith("//") and "#define" not in l)
-            found = set()
-            for m in re.finditer(r"(?:SHAPE[A-Z0-9]*\(|go[x4]?<)\s*%s\s*,\s*(\d+)\s*,\s*(\d+)\s*,\s*(\d+)" % ctype, text):
-                found.add(tuple(int(v) for v in m.groups()))
-            out[name] = frozenset(found)
-        _tables["nd2z"] = out
-    return _tables["nd2z"][prec]
-
-
-def nd2p_shapes(prec):
-    """(x, y, z) with a dense split-complex instance on 16-byte plane accesses, read off csrc/fft_nd2p.hip"""
-    if "nd2p" not in _tables:
-        import os
-        import re
-        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "pyfft_amd", "csrc", "fft_nd2p.hip")
-        text = open(path).read()
-        _tables["nd2p"] = {name: frozenset(tuple(int(v) for v in m.groups())
-                                             for m in re.finditer(r"(?:ALL|BIG)\(%s,\s*(\d+),\s*(\d+),\s*(\d+)\)" % ctype, text))
-                           for name, ctype in (("f32", "float"), ("f64", "double"))}
-    return _tables["nd2p"][prec]
-
-
-def nd2zp_shapes(prec):
-    """(x, y, z) with a several-work-groups-per-transform instance for dense split-complex planes, read off csrc/fft_nd2zp.hip"""
-    if "nd2zp" not in _tables:
-        import os
-        import re
-        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "pyfft_amd", "csrc", "fft_nd2zp.hip")
-        text = "\n".join(l for l in open(path).read().splitlines() if not l.lstrip().startswith("//") and "#define" not in l)
-        _tables["nd2zp"] = {name: frozenset(tuple(int(v) for v in m.groups())
-                                              for m in re.finditer(r"SHAPE[L4]?\(%s,\s*\d,\s*(\d+),\s*(\d+),\s*(\d+)\)" % ctype, text))
-                            for name, ctype in (("f32", "float"), ("f64", "double"))}
-    return _tables["nd2zp"][prec]
-
-
-def _nd_key(prec, lay, x, y, z):
-    """The instance an N-D pass of this shape runs: the shape's own fixed instance (interleaved: the generated tables; planes: the tiled
-    fixed-shape kernel where it takes dense planes), else the ONE run-time-shaped kernel, whose instances differ by the tile's size class."""
+def nd_kernel(d, aliased, small_launch=None, variant=None):
+    """The kernel form (N.ND_KERNEL_*) the library runs for the ND pass descriptor `d`: mifft_nd_kernel, the selector mifft_launch_pass
+    itself goes through.  aliased: bit 0 in0 == out0, bit 1 in1 == out1.  small_launch: override the descriptor's write-through mark (what
+    the plan sets for launches of up to write_through_max per side); variant: override its variant (0: the shape's own instance, not the
+    plan's per-batch choice of the run-time-shaped kernel in its place).  A negative code: the launch would be refused."""
+    import ctypes
     from pyfft_amd import _native as N
-    p = N.F64 if prec == "f64" else N.F32
-    if lay == "interleaved":
-        if (x, y, z) in fixed_nd_shapes(prec) or N.lib.mifft_nd_shape_supported(p, x, y, z, 0) != 0:
-            return ("nd_fixed", prec, lay, x, y, z)
-    elif (x, y, z) in nd2p_shapes(prec):
+    d = type(d).from_buffer_copy(d)
+    if small_launch is not None:
+        d.flags = (d.flags | N.FLAG_WRITE_THROUGH) if small_launch else (d.flags & ~N.FLAG_WRITE_THROUGH)
+    if variant is not None:
+        d.variant = variant
+    return N.lib.mifft_nd_kernel(ctypes.byref(d), aliased)
+
+
+def nd_pass(prec, x, y, z, planes=False):
+    """a dense ND pass descriptor of the shape, interleaved or planes on both sides (tables: any non-null address; nothing is launched)"""
+    from pyfft_amd import _native as N
+    d = N.MifftPass()
+    d.kind, d.precision, d.layout = N.PASS_ND, (N.F64 if prec == "f64" else N.F32), (N.SPLIT if planes else N.INTERLEAVED)
+    d.L, d.M, d.S, d.outer, d.scale = x, y, z, 4, 1.0
+    d.outer_stride_in = d.outer_stride_out = x * y * z
+    d.tw_L = d.tw_lo = d.tw_hi = 4096
+    return d
+
+
+def nd_instances(form, prec):
+    """every (x, y, z) of up to 2^MAX_LOG2_POINTS points that runs the several-work-groups form N.ND_KERNEL_ND2Z (interleaved) /
+    N.ND_KERNEL_ND2ZP (planes) in a small out-of-place launch: the whole instance table of that form, asked of the library"""
+    from pyfft_amd import _native as N
+    out = set()
+    for lx in range(MAX_LOG2_POINTS + 1):
+        for ly in range(MAX_LOG2_POINTS + 1 - lx):
+            for lz in range(MAX_LOG2_POINTS + 1 - lx - ly):
+                xyz = (1 << lx, 1 << ly, 1 << lz)
+                if nd_kernel(nd_pass(prec, *xyz, planes=form == N.ND_KERNEL_ND2ZP), 0, small_launch=True) == form:
+                    out.add(xyz)
+    return frozenset(out)
+
+
+def _nd_key(d):
+    """The instance an N-D pass of the plan runs in place: the shape's own fixed instance (interleaved: the generated tables; planes: the
+    dense 16-byte kernel, or the tiled fixed-shape kernel where it takes dense planes), else the ONE run-time-shaped kernel, whose instances
+    differ by the tile's size class.  A shape whose only kernel runs out of place is keyed by its shape too.  The answer is the library's
+    (mifft_nd_kernel) for variant 0 of the pass: the key names the shape's instance, not the plan's per-batch choice of the run-time-shaped
+    kernel in its place (variant 1, the tuning table's "nd_generic" lists)."""
+    from pyfft_amd import _native as N
+    prec = "f64" if d.precision == N.F64 else "f32"
+    lay = "split" if d.layout == N.SPLIT else "interleaved"
+    x, y, z = int(d.L), int(d.M), int(d.S)
+    form = nd_kernel(d, 3, variant=0)
+    if form == N.ND_KERNEL_ND2P:
         return ("nd_planes16", prec, x, y, z)
-    elif x * (8 if prec == "f64" else 4) >= 128 and N.lib.mifft_nd_tiled_supported(p, x, y, z) == 0:
-        return ("nd_fixed", prec, lay, x, y, z)
-    elif N.lib.mifft_nd_shape_supported(p, x, y, z, 0) != 0:
+    if form != N.ND_KERNEL_ND:
+        assert form in (N.ND_KERNEL_ND2, N.ND_KERNEL_ND2T, N.E_UNSUPPORTED), (form, N.last_error())
         return ("nd_fixed", prec, lay, x, y, z)
     n = x * y * z
     return ("nd_generic", prec, lay, "dims%d" % ((x > 1) + (y > 1) + (z > 1)), "log2n=%d" % (n.bit_length() - 1))
 
 
-def _chain_keys(plan, chain):
-    """one key per LAUNCH of a chain"""
+def _chain_keys(plan, chain, batch=1, first=0):
+    """one key per LAUNCH of a chain: plan._kernels[first:], or a pass list without ND passes"""
     from pyfft_amd import _native as N
     p = plan._params
     prec = "f64" if p.precision == N.F64 else "f32"
@@ -149,7 +148,7 @@ def _chain_keys(plan, chain):
             i += 2
             continue
         if k.kind == N.PASS_ND:
-            keys.add(_nd_key(prec, lay, int(k.L), int(k.M), int(k.S)))
+            keys.add(_nd_key(plan._descriptors(int(batch), True, False)[first + i]))
         elif k.kind == N.PASS_ROW:
             keys.add(("row", prec, lay, int(k.L)))
         else:
@@ -185,7 +184,7 @@ def keys_of_plan(plan, batch, mode="auto"):
     """keys_of for a given plan: one on the model of the full part (plan_for), or a device plan (what that device's planner selects)"""
     keys = set()
     if mode in ("chain", "pipelined"):
-        return _chain_keys(plan, plan._kernels)
+        return _chain_keys(plan, plan._kernels, batch)
     if mode == "fused":
         k = _persistent_key(plan)
         return {k} if k is not None else set()
@@ -196,23 +195,23 @@ def keys_of_plan(plan, batch, mode="auto"):
         pk = _persistent_key(plan)
         keys.add(pk)
         keys.add(("plane_fused",) + pk[1:4])
-        keys |= _chain_keys(plan, plan._kernels[2:])
+        keys |= _chain_keys(plan, plan._kernels[2:], batch, 2)
     elif strat[0] in plan.PERSISTENT:
         keys.add(_persistent_key(plan))
     else:
-        keys |= _chain_keys(plan, plan._kernels)
+        keys |= _chain_keys(plan, plan._kernels, batch)
     from pyfft_amd import _native as N
     p = plan._params
     prec = "f64" if p.precision == N.F64 else "f32"
     if plan._runs_oop_nd(int(batch)):
         keys.add(("nd_oop", prec + ("_planes" if p.split else ""), int(p.x), int(p.y), int(p.z)))
-    # a one-launch plan of split-complex planes with a several-work-groups instance (csrc/fft_nd2zp.hip): its out-of-place executes
-    if p.split and len(plan._kernels) == 1 and plan._kernels[0].kind == N.PASS_ND and (int(p.x), int(p.y), int(p.z)) in nd2zp_shapes(prec):
-        keys.add(("nd2zp", prec, int(p.x), int(p.y), int(p.z)))
-    # a one-launch plan of a shape with a several-work-groups-per-transform instance: its OUT-OF-PLACE executes take that instance inside
-    # the library (csrc/mifft_runtime.cpp launch_nd; small launches only for some shapes -- the tests assert which)
-    if not p.split and len(plan._kernels) == 1 and plan._kernels[0].kind == N.PASS_ND and (int(p.x), int(p.y), int(p.z)) in nd2z_shapes(prec):
-        keys.add(("nd2z", prec, int(p.x), int(p.y), int(p.z)))
+    # a one-launch plan of a shape with a several-work-groups-per-transform instance (csrc/fft_nd2z.hip; split-complex planes:
+    # csrc/fft_nd2zp.hip): its OUT-OF-PLACE executes take that instance inside the library (mifft_nd_kernel, the selector of
+    # mifft_launch_pass; for some interleaved shapes in small launches only -- the tests assert which -- so the key is asked for those)
+    if len(plan._kernels) == 1 and plan._kernels[0].kind == N.PASS_ND:
+        form = nd_kernel(plan._descriptors(int(batch), False, False)[0], 0, small_launch=True, variant=0)     # (variant 0: as _nd_key)
+        if form in (N.ND_KERNEL_ND2Z, N.ND_KERNEL_ND2ZP):
+            keys.add(("nd2zp" if form == N.ND_KERNEL_ND2ZP else "nd2z", prec, int(p.x), int(p.y), int(p.z)))
     return keys
 
 

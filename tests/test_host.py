@@ -76,6 +76,31 @@ def test_launch_rejects_bad_descriptors_without_touching_the_gpu():
     assert N.lib.mifft_launch_pass(ctypes.byref(p), 8, None, 16, None, None) == N.E_INVALID   # misaligned
     p.kind, p.M, p.S = N.PASS_COL, 4, 1
     assert N.lib.mifft_launch_pass(ctypes.byref(p), 16, None, 32, None, None) == N.E_INVALID  # tables missing
+    p.precision = 7
+    assert N.lib.mifft_launch_pass(ctypes.byref(p), 16, None, 32, None, None) == N.E_INVALID and "bad precision 7" in N.last_error()
+    # an ND pass: mifft_nd_kernel gives the launch's own refusals, in the launch's order, and the form of what it would run
+    nd = N.MifftPass()
+    nd.kind, nd.precision, nd.layout, nd.L, nd.M, nd.S, nd.outer, nd.scale = N.PASS_ND, N.F32, N.INTERLEAVED, 256, 256, 1, 4, 1.0
+    nd.outer_stride_in = nd.outer_stride_out = 65536
+    nd.tw_L = nd.tw_lo = 16
+    assert N.lib.mifft_nd_kernel(ctypes.byref(nd), 0) == N.ND_KERNEL_ND2Z                      # four work-groups per transform: out of place only
+    for call in (lambda: N.lib.mifft_nd_kernel(ctypes.byref(nd), 1), lambda: N.lib.mifft_launch_pass(ctypes.byref(nd), 16, None, 16, None, None)):
+        assert call() == N.E_UNSUPPORTED and "out of place only" in N.last_error(), N.last_error()
+    assert N.lib.mifft_launch_pass(ctypes.byref(nd), 16, None, 24, None, None) == N.E_INVALID and "16-byte aligned" in N.last_error()
+    nd.outer_stride_in = 65537
+    for call in (lambda: N.lib.mifft_nd_kernel(ctypes.byref(nd), 0), lambda: N.lib.mifft_launch_pass(ctypes.byref(nd), 16, None, 32, None, None)):
+        assert call() == N.E_INVALID and "outer strides must be even" in N.last_error()
+    nd.outer_stride_in, nd.M = 65536, 512
+    for call in (lambda: N.lib.mifft_nd_kernel(ctypes.byref(nd), 0), lambda: N.lib.mifft_launch_pass(ctypes.byref(nd), 16, None, 32, None, None)):
+        assert call() == N.E_UNSUPPORTED and "no kernel for 256 x 512 x 1 (131072 points)" in N.last_error()
+    nd.M, nd.tw_lo = 16, None
+    assert N.lib.mifft_nd_kernel(ctypes.byref(nd), 0) == N.E_INVALID and "twiddle table missing" in N.last_error()
+    nd.tw_lo, nd.layout = 16, N.SPLIT
+    assert N.lib.mifft_nd_kernel(ctypes.byref(nd), 3) == N.ND_KERNEL_ND                        # (4096 points, 1 KiB plane rows without an instance)
+    assert N.lib.mifft_launch_pass(ctypes.byref(nd), 16, None, 32, 48, None) == N.E_INVALID and "imaginary planes" in N.last_error()
+    p.kind, p.precision, p.M, p.S = N.PASS_ROW, N.F32, 1, 1
+    assert N.lib.mifft_nd_kernel(ctypes.byref(p), 0) == N.E_INVALID and "not an ND pass" in N.last_error()
+    assert N.lib.mifft_nd_kernel(None, 0) == N.E_INVALID
     with pytest.raises(ValueError):
         N.check(N.E_INVALID, "x")
     with pytest.raises(RuntimeError):
@@ -461,6 +486,94 @@ def test_round3_entry_points_reject_bad_arguments_without_touching_the_gpu():
     assert N.lib.mifft_launch_bluestein_rows(N.F32, 1009, 2000, 4, 1009, 1009, 16, 16, 16, 16, 16, 0, 1.0, None) == N.E_UNSUPPORTED  # m < 2n-1
     assert N.lib.mifft_launch_bluestein_rows(N.F32, 1009, 2048, 4, 1000, 1009, 16, 16, 16, 16, 16, 0, 1.0, None) == N.E_INVALID      # stride < n
     assert N.lib.mifft_launch_bluestein_rows(N.F32, 1009, 2048, 4, 1009, 1009, 16, 16, 16, None, 16, 0, 1.0, None) == N.E_INVALID
+    # the checks every entry point shares -- precision, alignment to one complex number (fp64: 16 bytes), sizes that overflow --
+    # keep their entry point's code and message
+    big = 1 << 61
+    for rc, code, what in (
+            (lambda: N.lib.mifft_launch_mixed_rows(N.F64, 1000, 4, 1000, 1000, 24, 32, 16, 0, 1.0, None), N.E_INVALID, "mixed rows: data buffers must be aligned to one complex number"),
+            (lambda: N.lib.mifft_launch_mixed_rows(N.F32, 1000, 4, 1000, 1000, 20, 32, 16, 0, 1.0, None), N.E_INVALID, "mixed rows: data buffers must be aligned to one complex number"),
+            (lambda: N.lib.mifft_launch_mixed_rows(N.F32, 1000, big, 1000, 1000, 16, 32, 16, 0, 1.0, None), N.E_INVALID, "mixed rows: rows * stride overflows"),
+            (lambda: N.lib.mifft_launch_mixed_rows(N.F32, 1000, 4, 1000, 1008, 16, 16, 16, 0, 1.0, None), N.E_INVALID, "mixed rows: an in-place call needs equal row strides"),
+            (lambda: N.lib.mifft_launch_mixed_rows(7, 1000, 4, 1000, 1000, 16, 32, 16, 0, 1.0, None), N.E_UNSUPPORTED, "mixed rows: no kernel for n = 1000"),
+            (lambda: N.lib.mifft_launch_mixed_lines(N.F32, 1000, big, 4, 16, 32, 16, 0, 0, 1.0, None), N.E_INVALID, "mixed lines: outer * inner * n overflows"),
+            (lambda: N.lib.mifft_launch_mixed_lines(N.F64, 1000, 4, 4, 16, 40, 16, 0, 0, 1.0, None), N.E_INVALID, "mixed lines: data buffers must be aligned"),
+            (lambda: N.lib.mifft_launch_mixed_long(N.F64, 120, 250, 4, 16, 32, 56, 16, 16, 16, 16, 8, 0, 1.0, None), N.E_INVALID, "mixed long: data buffers must be aligned to one complex number"),
+            (lambda: N.lib.mifft_launch_mixed_long(N.F32, 120, 250, big, 16, 32, 48, 16, 16, 16, 16, 8, 0, 1.0, None), N.E_INVALID, "mixed long: batch * n overflows"),
+            (lambda: N.lib.mifft_launch_mixed_nd(N.F64, 70, 70, 1, 4, 24, 32, 16, 16, None, 0, 1.0, None), N.E_INVALID, "mixed nd: data buffers must be aligned"),
+            (lambda: N.lib.mifft_launch_mixed_nd(N.F32, 100, 100, 1, big, 16, 32, 16, 16, None, 0, 1.0, None), N.E_INVALID, "mixed nd: bad transform count"),
+            (lambda: N.lib.mifft_launch_bluestein_rows(N.F64, 1009, 2048, 4, 1009, 1009, 16, 24, 16, 16, 16, 0, 1.0, None), N.E_INVALID, "bluestein rows: data buffers must be aligned"),
+            (lambda: N.lib.mifft_launch_bluestein_rows(N.F32, 1009, 2048, big, 1009, 1009, 16, 32, 16, 16, 16, 0, 1.0, None), N.E_INVALID, "bluestein rows: rows * stride overflows"),
+            (lambda: N.lib.mifft_launch_nd_tiled(ctypes.byref(nd), ctypes.byref(t), 16, 24, None), N.E_UNSUPPORTED, "nd_tiled: no kernel for tiles of 16 x 4 x 1")):
+        assert rc() == code and what in N.last_error(), (what, N.last_error())
+    nd.M = 16
+    assert N.lib.mifft_launch_nd_tiled(ctypes.byref(nd), ctypes.byref(t), 16, 24, None) == N.E_INVALID and "data buffers must be 16-byte aligned" in N.last_error()
+    nd.precision = 7
+    assert N.lib.mifft_launch_nd_tiled(ctypes.byref(nd), ctypes.byref(t), 16, 32, None) == N.E_INVALID and "bad precision 7" in N.last_error()
+    assert N.lib.mifft_aux_count_mismatch(16, 24, 64, 8, None) == N.E_INVALID and "whole 16-byte words" in N.last_error()
+    assert N.lib.mifft_aux_count_mismatch(16, 32, 64, 12, None) == N.E_INVALID and "8-byte aligned counter" in N.last_error()
+    for query in (lambda: N.lib.mifft_nd_shape_supported(7, 16, 16, 1, 0), lambda: N.lib.mifft_nd_tiled_supported(7, 16, 16, 1), lambda: N.lib.mifft_mixed_supported(7, 1000),
+                  lambda: N.lib.mifft_mixed_radices(7, 1000, (ctypes.c_int32 * N.MIFFT_MIXED_MAX_STAGES)()), lambda: N.lib.mifft_mixed_long_split(7, 30000, ctypes.byref(n1), ctypes.byref(n2)),
+                  lambda: N.lib.mifft_bluestein_padded(7, 1009, ctypes.byref(m)), lambda: N.lib.mifft_mixed_nd_supported(7, 100, 100, 1),
+                  lambda: N.lib.mifft_pair_kernel_supported(7, N.INTERLEAVED, 0, 256, 32, 8),
+                  lambda: N.lib.mifft_launch_bluestein_rows(7, 1009, 2048, 4, 1009, 1009, 16, 32, 16, 16, 16, 0, 1.0, None)):
+        assert query() == N.E_UNSUPPORTED
+    # ... and the extension entry points: alignment, overlapping byte ranges (one complex number into the other side, or half way), overflow,
+    # precision -- each refused with its entry point's own message before anything is launched
+    A, B, T = 1 << 20, 1 << 21, 1 << 22              # (addresses far apart; nothing is dereferenced)
+
+    def real_post(**kw):
+        d = N.MifftRealPost(precision=N.F32, inverse=0, nx=16, ny=1, nz=1, outer=2, stride_in=8, stride_out=9, in_=A, out=B, tw=T, scale=1.0)
+        for k, v in kw.items():
+            setattr(d, k, v)
+        return N.lib.mifft_launch_real_post(ctypes.byref(d), None)
+
+    def r2r(post, **kw):
+        d = N.MifftR2rStep(precision=N.F32, inverse=0, kind=0, ndim=1, n=(16, 0, 0), outer=2, in_=A, out=B, tw=T, scale=1.0)
+        for k, v in kw.items():
+            setattr(d, k, v)
+        return (N.lib.mifft_launch_r2r_post if post else N.lib.mifft_launch_r2r_pre)(ctypes.byref(d), None)
+
+    for rc, code, what in (
+            (lambda: real_post(in_=A + 4), N.E_INVALID, "real post: buffers must be aligned to one complex number"),
+            (lambda: real_post(precision=N.F64, tw=T + 8), N.E_INVALID, "real post: buffers must be aligned to one complex number"),
+            (lambda: real_post(out=A + 64), N.E_INVALID, "real post: input and output overlap (out of place only)"),
+            (lambda: real_post(out=A - 136), N.E_INVALID, "real post: input and output overlap (out of place only)"),       # (the last output number reaches the input)
+            (lambda: real_post(outer=big), N.E_INVALID, "real post: items * pitch overflows"),
+            (lambda: real_post(precision=7), N.E_INVALID, "real post: bad precision 7"),
+            (lambda: N.lib.mifft_launch_real_row(N.F32, 1024, 0, 4, A + 4, B, T, T, 1.0, None), N.E_INVALID, "real row: buffers must be aligned to one complex number"),
+            (lambda: N.lib.mifft_launch_real_row(N.F64, 1024, 0, 4, A, B, T, T + 8, 1.0, None), N.E_INVALID, "real row: buffers must be aligned to one complex number"),
+            (lambda: N.lib.mifft_launch_real_row(N.F32, 1024, 0, 4, A, A + 4 * 512 * 8 - 8, T, T, 1.0, None), N.E_INVALID, "real row: input and output overlap (out of place only)"),
+            (lambda: N.lib.mifft_launch_real_row(N.F32, 1024, 0, big, A, B, T, T, 1.0, None), N.E_INVALID, "real row: rows * n overflows"),
+            (lambda: N.lib.mifft_launch_real_row(7, 1024, 0, 4, A, B, T, T, 1.0, None), N.E_INVALID, "real row: bad precision 7"),
+            (lambda: N.lib.mifft_launch_conv_row(N.F32, 0, 1024, 4, A + 4, B, T, 0, 0, T + 65536, None, 1.0, None), N.E_INVALID, "conv row: buffers must be aligned to one complex number"),
+            (lambda: N.lib.mifft_launch_conv_row(N.F64, 0, 1024, 4, A, B, T + 8, 0, 0, T + 65536, None, 1.0, None), N.E_INVALID, "conv row: buffers must be aligned to one complex number"),
+            (lambda: N.lib.mifft_launch_conv_row(N.F32, 0, 1024, 4, A, A + 8, T, 0, 0, T + 65536, None, 1.0, None), N.E_INVALID, "conv row: input and output overlap without being equal"),
+            (lambda: N.lib.mifft_launch_conv_row(N.F32, 0, 1024, 4, A, A, A + 4 * 1024 * 8 - 8, 0, 0, T, None, 1.0, None), N.E_INVALID, "conv row: the spectrum overlaps the data"),
+            (lambda: N.lib.mifft_launch_conv_row(N.F32, 0, 1024, 4, A, B, B - 1024 * 8 + 8, 0, 0, T, None, 1.0, None), N.E_INVALID, "conv row: the spectrum overlaps the data"),
+            (lambda: N.lib.mifft_launch_conv_row(N.F32, 0, 1024, big, A, B, T, 0, 0, T + 65536, None, 1.0, None), N.E_INVALID, "conv row: rows * n overflows"),
+            (lambda: N.lib.mifft_launch_conv_row(7, 0, 1024, 4, A, B, T, 0, 0, T + 65536, None, 1.0, None), N.E_INVALID, "conv row: bad precision 7"),
+            (lambda: N.lib.mifft_aux_mul_spectrum(N.F32, A + 4, B, 4, 16, 0, 0, 1.0, None), N.E_INVALID, "mul_spectrum: buffers must be aligned to one complex number"),
+            (lambda: N.lib.mifft_aux_mul_spectrum(N.F64, A, B + 8, 4, 16, 0, 0, 1.0, None), N.E_INVALID, "mul_spectrum: buffers must be aligned to one complex number"),
+            (lambda: N.lib.mifft_aux_mul_spectrum(N.F32, A, B, big, 16, 0, 0, 1.0, None), N.E_INVALID, "mul_spectrum: items * points overflows"),
+            (lambda: N.lib.mifft_aux_mul_spectrum(7, A, B, 4, 16, 0, 0, 1.0, None), N.E_INVALID, "mul_spectrum: bad precision 7"),
+            (lambda: r2r(0, in_=A + 2), N.E_INVALID, "r2r pre: buffers must be aligned to one real (packed side: one complex) number"),
+            (lambda: r2r(0, out=B + 4), N.E_INVALID, "r2r pre: buffers must be aligned to one real (packed side: one complex) number"),     # (the packed side)
+            (lambda: r2r(1, precision=N.F64, tw=T + 8), N.E_INVALID, "r2r post: buffers must be aligned to one real (packed side: one complex) number"),
+            (lambda: r2r(0, out=A + 2 * 16 * 4 - 8), N.E_INVALID, "r2r pre: input and output overlap (out of place only)"),
+            (lambda: r2r(1, in_=B + 8), N.E_INVALID, "r2r post: input and output overlap (out of place only)"),
+            (lambda: r2r(0, outer=big), N.E_INVALID, "r2r pre: items * points overflows"),
+            (lambda: r2r(1, precision=7), N.E_INVALID, "r2r post: bad precision 7"),
+            (lambda: N.lib.mifft_launch_r2r_row(N.F32, 1024, 0, 0, 4, A + 8, B, T, T, T, None), N.E_INVALID, "r2r row: data must be 16-byte aligned, tables aligned to one complex number"),
+            (lambda: N.lib.mifft_launch_r2r_row(N.F64, 1024, 0, 0, 4, A, B, T, T, T + 8, None), N.E_INVALID, "r2r row: data must be 16-byte aligned, tables aligned to one complex number"),
+            (lambda: N.lib.mifft_launch_r2r_row(N.F32, 1024, 0, 0, 4, A, A + 4 * 1024 * 4 - 16, T, T, T, None), N.E_INVALID, "r2r row: input and output overlap without being the same buffer"),
+            (lambda: N.lib.mifft_launch_r2r_row(N.F32, 1024, 0, 0, big, A, B, T, T, T, None), N.E_INVALID, "r2r row: rows * n overflows"),
+            (lambda: N.lib.mifft_launch_r2r_row(7, 1024, 0, 0, 4, A, B, T, T, T, None), N.E_INVALID, "r2r row: bad precision 7"),
+            (lambda: N.lib.mifft_launch_half(1024, 1, 1, 0, 0, 4, A + 8, B, T, None, None, 1.0, None), N.E_INVALID, "half: buffers must be 16-byte aligned"),
+            (lambda: N.lib.mifft_launch_half(1024, 1, 1, 0, 0, 4, A, B, T + 4, None, None, 1.0, None), N.E_INVALID, "half: tables must be 8-byte aligned"),
+            (lambda: N.lib.mifft_launch_half(1024, 1, 1, 0, 0, 4, A, A + 4 * 1024 * 4 - 16, T, None, None, 1.0, None), N.E_INVALID, "half: input and output overlap (in place is exact aliasing only)"),
+            (lambda: N.lib.mifft_launch_half(1024, 1, 1, 0, 0, 4, B, B - 4 * 1024 * 4 + 16, T, None, None, 1.0, None), N.E_INVALID, "half: input and output overlap (in place is exact aliasing only)"),
+            (lambda: N.lib.mifft_launch_half(1024, 1, 1, 0, 0, big, A, B, T, None, None, 1.0, None), N.E_INVALID, "half: transforms * points overflows")):
+        assert rc() == code and what in N.last_error(), (what, N.last_error())
     # the fp64 strided passes of 2048 points exist, the pair split answers per layout
     assert N.lib.mifft_pass_supported(N.PASS_COL, N.F64, 2048, 0) == 0
     assert N.lib.mifft_pair_split(N.F64, N.SPLIT, 256, 256, 256) == 64 and N.lib.mifft_pair_split(N.F32, N.INTERLEAVED, 128, 128, 128) == 32
@@ -558,6 +671,8 @@ def test_persistent_entry_points_reject_bad_arguments_without_touching_the_gpu()
         assert what in N.last_error(), N.last_error()
     assert N.lib.mifft_launch_fused2(byref(p0), byref(p1), 16, None, 32, None, 64, None, 28, 14, None, 512, None) == N.E_INVALID
     assert N.lib.mifft_launch_fused2(byref(p0), byref(p1), 16, None, 32, None, 64, None, 14, 14, byref(ok), 512, None) == N.E_INVALID   # lag == ring
+    assert N.lib.mifft_launch_fused2(byref(p0), byref(p1), 16, None, 40, None, 64, None, 28, 14, byref(ok), 512, None) == N.E_INVALID
+    assert "data buffers must be 16-byte aligned" in N.last_error(), N.last_error()
     # two alternating counter sets need an error word of their own (the next launch zeroes the default one, word 1 of line 0)
     assert N.lib.mifft_launch_fused2(byref(p0), byref(p1), 16, None, 32, None, 64, None, 28, 14, byref(N.MifftFusedSync(4096, 8192, None)), 512, None) == N.E_INVALID
     assert "error word of their own" in N.last_error(), N.last_error()
@@ -595,6 +710,8 @@ def test_persistent_entry_points_reject_bad_arguments_without_touching_the_gpu()
     assert N.lib.mifft_launch_fused_pair(descs, 16, None, 32, None, 32, 4, 2, byref(ok), 512, None) == N.E_INVALID and "ring" in N.last_error()
     assert N.lib.mifft_launch_fused_pair(descs, 16, None, 32, None, 64, 4, 4, byref(ok), 512, None) == N.E_INVALID
     assert N.lib.mifft_launch_fused_pair(descs, 16, None, 32, None, 64, 4, 2, None, 512, None) == N.E_INVALID
+    assert N.lib.mifft_launch_fused_pair(descs, 16, None, 32, None, 72, 4, 2, byref(ok), 512, None) == N.E_INVALID
+    assert "data buffers must be 16-byte aligned" in N.last_error(), N.last_error()
     descs[1].L, descs[1].M = 64, 2                      # not the split the library's kernels use
     assert N.lib.mifft_launch_fused_pair(descs, 16, None, 32, None, 64, 4, 2, byref(ok), 512, None) in (N.E_INVALID, N.E_UNSUPPORTED)
     # device properties carry the memory-system fields the planner reads
@@ -711,6 +828,38 @@ def test_strategy_snapshot_of_the_table_driven_planner_on_one_library():
     assert not bad, bad[:10]
     assert not any(g[5][0] == "fused2x" for g in got) and sum(1 for w in want if w[5][0] == "fused2x") == 18
     assert set(r[5][0] for r in want) == {"chain", "pipelined", "fused2", "fusedp", "fused2x"}
+
+
+def test_nd_kernel_snapshot():
+    """mifft_nd_kernel -- the one selector mifft_launch_pass runs an ND pass through -- answers what the library launched before the
+    selection was written in one place: tests/golden/nd_kernel_snapshot.json.gz holds every point whose form is a fixed one (written from
+    the earlier code, see make_nd_kernel_snapshot.py) under the default switches and the five settings the rule reads; every other point
+    runs the run-time-shaped kernel exactly when the shape has at most mifft_nd_max_points_for points (and at least the 4 an ND pass needs), and is refused otherwise."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    import make_nd_kernel_snapshot as snap
+    from pyfft_amd import _native as N
+    want = snap.load()
+    assert want["forms"] == list(snap.FORMS) and want["settings"] == [list(s) for s in snap.SETTINGS]
+    max_points = {prec: N.lib.mifft_nd_max_points_for(prec) for prec in (N.F32, N.F64)}
+    count = {"nd": 0, "refused": 0}
+    wrong = []
+
+    def unlisted(prec, x, y, z, code):
+        count["nd" if code == N.ND_KERNEL_ND else "refused"] += 1
+        if (code == N.ND_KERNEL_ND) != (4 <= x * y * z <= max_points[prec]) or (code != N.ND_KERNEL_ND and code != N.E_UNSUPPORTED):
+            wrong.append((prec, x, y, z, code))
+
+    got = snap.enumerate_library(unlisted)
+    assert not wrong, wrong[:10]
+    assert got == want["points"], sorted(k for k in set(got) | set(want["points"]) if got.get(k) != want["points"].get(k))[:10]
+    # not vacuous: every form occurs, the fixed ones in the file
+    seen = {}
+    for group in got.values():
+        for form, shapes in group.items():
+            seen[form] = seen.get(form, 0) + len(shapes)
+    assert set(seen) == set(snap.FORMS) - {"nd"} and all(v > 0 for v in seen.values()), seen
+    assert count["nd"] > 100000 and count["refused"] > 100000 and sum(seen.values()) + count["nd"] + count["refused"] == 1404000
 
 
 def test_planner_follows_a_doctored_tuning_table():

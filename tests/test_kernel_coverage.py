@@ -20,7 +20,7 @@ def test_every_kernel_instance_a_default_plan_selects_has_a_default_gpu_test():
     assert kinds["pairXY"] >= 15 and kinds["pairYZ"] >= 25 and kinds["persistent"] >= 60 and kinds["nd_oop"] >= 20 and kinds["nd_fixed"] >= 350 and kinds["nd2z"] >= 30 and kinds["nd_generic"] >= 20
     assert kinds["row"] >= 40 and kinds["col"] >= 80
     for prec in ("f32", "f64"):            # every instance of the several-work-groups tables is somebody's default choice (or dead code)
-        for xyz in KC.nd2z_shapes(prec):
+        for xyz in KC.nd_instances(N.ND_KERNEL_ND2Z, prec):
             assert ("nd2z", prec) + xyz in uni or ("nd_oop", prec) + xyz in uni, (prec, xyz)
     missing = sorted(((k, ex) for k, ex in uni.items() if k not in cov), key=str)
     assert not missing, "kernel instances no default-collected GPU test runs (key, an example plan): %r" % (missing[:40],)

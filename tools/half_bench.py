@@ -31,7 +31,7 @@ def _shapes(argv):
 
 def _oop_runs_nd2z(N, shape):
     """The complex64 plan's out-of-place N-D pass at this size runs several work-groups per transform (fft_nd2z.hpp): the one-tile-per-CU
-    shapes beyond the run-time-shaped kernel's 16384 points where that kernel is preferred at every buffer size (launch_nd)."""
+    shapes beyond the run-time-shaped kernel's 16384 points where that kernel is preferred at every buffer size (select_nd, csrc/mifft_runtime.cpp)."""
     x, y, z = tuple(reversed(shape)) + (1,) * (3 - len(shape))
     return len(shape) > 1 and x * y * z > N.lib.mifft_nd_max_points_for(N.F32) and \
         N.lib.mifft_nd_shape_supported(N.F32, x, y, z, N.VARIANT_OUT_OF_PLACE_ANY_SIZE) == 0

@@ -1,11 +1,13 @@
-"""Host cost of one asynchronous execute() (a 16-point plan, batch 1: the device work is negligible).  Development tool."""
+"""Host cost of one asynchronous execute() (batch 1 of a tiny plan: the device work is negligible).  Development tool.
+--shape: the plan's shape, default 16 (one ROW pass); 16,16 is one ND pass."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy
 from pyfft_amd.hip import Plan, DeviceArray, Stream
-a = DeviceArray((16,), numpy.complex64); b = DeviceArray((16,), numpy.complex64)
+shape = tuple(int(v) for v in sys.argv[sys.argv.index("--shape") + 1].split(",")) if "--shape" in sys.argv else (16,)
+a = DeviceArray(shape, numpy.complex64); b = DeviceArray(shape, numpy.complex64)
 s = Stream()
-plan = Plan((16,), dtype=numpy.complex64, stream=s)
+plan = Plan(shape, dtype=numpy.complex64, stream=s)
 for n in (2000, 20000):
     plan.execute(a, b); s.synchronize()
     t0 = time.perf_counter()
@@ -14,4 +16,4 @@ for n in (2000, 20000):
     t1 = time.perf_counter()
     s.synchronize()
     t2 = time.perf_counter()
-    print("%d executes: %.2f us per call on the host (%.2f us with the final sync)" % (n, (t1 - t0) / n * 1e6, (t2 - t0) / n * 1e6))
+    print("%s: %d executes: %.2f us per call on the host (%.2f us with the final sync)" % (shape, n, (t1 - t0) / n * 1e6, (t2 - t0) / n * 1e6))
