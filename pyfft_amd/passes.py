@@ -242,7 +242,9 @@ def yz_pair_chain(x, y, z, precision, interleaved):
     """X passes, then COL y + COL z as one launch on whole (z, y) planes of 16 adjacent x (csrc/fft_pair.hpp PairYZ with the y axis
     unsplit): a 3-D shape with short y and z behind a long x in two launches instead of three."""
     if x <= row_max(precision, interleaved):
-        chain = [PassSpec(N.PASS_ROW, X_DIRECTION, x, x, 1, 1, y * z, x, True)]
+        # split planes: the pair reads interleaved data only (classify_pair, csrc/mifft_runtime.cpp), so the row pass in front of it must
+        # move the data to the plan's interleaved temp buffer -- a row that may stay in place leaves the pair on the user's planes
+        chain = [PassSpec(N.PASS_ROW, X_DIRECTION, x, x, 1, 1, y * z, x, interleaved)]
     else:
         chain = col_chain(X_DIRECTION, x, 1, y * z, precision, interleaved)
     chain += [PassSpec(N.PASS_COL, Y_DIRECTION, y, y, 1, x, z, y * x, True),

@@ -560,9 +560,11 @@ def _poison_layouts(batch):
     yield {j: ((0, numpy.nan) if j % 4 == 0 else (-1, numpy.inf)) for j in range(0, batch, 2)}
 
 
-def run_contract(plan, c, oop_differs, record_property):
+def run_contract(plan, c, inplace_too, record_property):
     """Steps 1-4 of the per-instance contract (tests/test_instances_gpu.py) on the buffers of `c` (a _Case) through `plan`.  Leaves the
-    clean forward result in c.ref; returns the reports [(step name, check_accuracy report)], which it also records."""
+    clean forward result in c.ref; returns the reports [(step name, check_accuracy report)], which it also records.  inplace_too: the
+    in-place executes are what the case is about (they run another instance than the out-of-place ones, or give the case's launch its
+    buffer sides): step 2 is held to the bound itself, and steps 3 and 4 run in place as well."""
     N = c.N
     batch = c.batch
     ins, outs = c.ins, c.outs
@@ -639,18 +641,18 @@ def run_contract(plan, c, oop_differs, record_property):
     run(outs)
     c._sync()
     c.guards(outs, "in-place forward")
-    if oop_differs:
+    if inplace_too:
         c.accuracy(outs, blk, what="in place")
     else:
         for b, r in zip(outs, c.ref):
             assert c.mismatches(b.ptr, r.ptr, c.plane_bytes) == 0, "in place differs from out of place"
 
-    # 3. + 4. out of place; and in place where that runs another instance (c.ref then holds the in-place result)
+    # 3. + 4. out of place; and in place where the case is about those executes (c.ref then holds the in-place result)
     blk3 = _block(c.cdt, c.count, 202)
     inv = inverse(False, blk3)
     isolation(False)
     reps = [("forward", fw), ("inverse", inv)]
-    if oop_differs:
+    if inplace_too:
         for b, x in zip(outs, c.x0):
             c._d2d(b.ptr, x.ptr, c.plane_bytes)
         run(outs)

@@ -14,6 +14,11 @@ collects (about half of the pass-pair instances had their only 
                                        tests' own parametrize marks through REGISTRY (one adapter per test function)
   audit_cases()                        for every key of universe(), the smallest case (shape, dtype, batch >= 3) that selects it: the
                                        cases of tests/test_instances_gpu.py, which holds each instance to the accuracy contract
+  launch_sides_of_plan(plan, batch, inplace)   {(key, (planes in, planes out, aliased))} of one execute: the buffer sides the plan's schedule
+                                       gives each launch, read off the plan's descriptors
+  sides_universe()                     every (key, sides) reachable by those shapes at batch 3 and universe()'s batches, in either placement
+  sides_audit_cases()                  the smallest case (shape, dtype, batch >= 3, placement) for every (key, sides) audit_cases() launches
+                                       in neither placement: the cases of test_instances_gpu.py::test_instance_sides
 
 The reference sweeps its kernels the same way, by shape lists: test/test_errors.py:125-145.
 """
@@ -130,36 +135,44 @@ def _nd_key(d):
     return ("nd_generic", prec, lay, "dims%d" % ((x > 1) + (y > 1) + (z > 1)), "log2n=%d" % (n.bit_length() - 1))
 
 
-def _chain_keys(plan, chain, batch=1, first=0):
-    """one key per LAUNCH of a chain: plan._kernels[first:], or a pass list without ND passes"""
+def _chain_launches(plan, chain, batch=1, first=0):
+    """[(key, index of the launch's first descriptor, of its last)] per LAUNCH of a chain: plan._kernels[first:], or a pass list without
+    ND passes.  The indices count from the start of plan._kernels (a pass pair: two descriptors, one launch)."""
     from pyfft_amd import _native as N
     p = plan._params
     prec = "f64" if p.precision == N.F64 else "f32"
     lay = "split" if p.split else "interleaved"
-    keys, i = set(), 0
+    out, i = [], 0
     while i < len(chain):
         k = chain[i]
         if k.pair_with_next:
             k2 = chain[i + 1]
             if k.kind == N.PASS_ROW:
-                keys.add(("pairXY", prec, lay, int(k.L), int(k2.L), int(k2.M)))        # (nx, R0, R1): mifft_pair_kernel_supported kind 0
+                key = ("pairXY", prec, lay, int(k.L), int(k2.L), int(k2.M))        # (nx, R0, R1): mifft_pair_kernel_supported kind 0
             else:
-                keys.add(("pairYZ", prec, lay, int(k.S), int(k.L), int(k2.L)))         # (S0, R1, nz): kind 1
+                key = ("pairYZ", prec, lay, int(k.S), int(k.L), int(k2.L))         # (S0, R1, nz): kind 1
+            out.append((key, first + i, first + i + 1))
             i += 2
             continue
         if k.kind == N.PASS_ND:
-            keys.add(_nd_key(plan._descriptors(int(batch), True, False)[first + i]))
+            key = _nd_key(plan._descriptors(int(batch), True, False)[first + i])
         elif k.kind == N.PASS_ROW:
-            keys.add(("row", prec, lay, int(k.L)))
+            key = ("row", prec, lay, int(k.L))
         else:
             # a strided pass: its length, whether it carries the inter-pass twiddle (M > 1), and the class of its stride (S == 1: the
             # transposing first pass of a long contiguous axis; S < 16: columns narrower than a tile; else whole 16-column tiles)
             # (fp32 interleaved 256 / 512 points with rows >= 2^16 points apart: the 32-column plain tiles of csrc/fft_col2_f32.hip)
             far = prec == "f32" and lay == "interleaved" and k.L in (256, 512) and k.M == 1 and k.S >= 65536
-            keys.add(("col", prec, lay, int(k.L), "twiddled" if k.M > 1 else "plain",
-                      "S1" if k.S == 1 else ("S<16" if k.S < 16 else ("S>=65536" if far else "S>=16"))))
+            key = ("col", prec, lay, int(k.L), "twiddled" if k.M > 1 else "plain",
+                   "S1" if k.S == 1 else ("S<16" if k.S < 16 else ("S>=65536" if far else "S>=16")))
+        out.append((key, first + i, first + i))
         i += 1
-    return keys
+    return out
+
+
+def _chain_keys(plan, chain, batch=1, first=0):
+    """one key per LAUNCH of a chain (_chain_launches)"""
+    return set(key for key, _, _ in _chain_launches(plan, chain, batch, first))
 
 
 def _persistent_key(plan):
@@ -215,6 +228,60 @@ def keys_of_plan(plan, batch, mode="auto"):
     return keys
 
 
+# ---- the buffer sides of a launch ----------------------------------------------------------------------------------------------------
+# A key says which kernel family, length and stride class a launch is; the plan's buffer schedule adds three run-time facts per launch
+# that the dispatcher and the kernels branch on (mifft_colr_eligible, mifft_col2x_f32_eligible, the a.split / a.split_out paths of
+# csrc/fft_tile.hpp, select_nd's alias bits): which side holds split planes, and whether the launch reads and writes one buffer.
+def _unit_sides(plan, d_first, d_last, inplace):
+    """(planes in, planes out, aliased) of a launch whose first / last descriptors are given (a pass pair: two; else the same one)"""
+    from pyfft_amd import _native as N
+    split = bool(plan._params.split)
+    src, dst = int(d_first.src), int(d_last.dst)
+    # (an in-place execute passes the user's buffer as both 0 and 1)
+    aliased = src == dst or (bool(inplace) and src in (0, 1) and dst in (0, 1))
+    return (split and not (d_first.flags & N.FLAG_SRC_INTERLEAVED), split and not (d_last.flags & N.FLAG_DST_INTERLEAVED), aliased)
+
+
+def launch_sides_of_plan(plan, batch, inplace):
+    """{(key, (planes in, planes out, aliased))} over the launches of ONE execute of `batch` items, in place or out of place: the keys
+    of keys_of_plan(plan, batch) that this placement launches, each with the sides read off the plan's own descriptors.  Persistent
+    launches and the one-launch out-of-place route (nd_oop, nd2z, nd2zp) work on the user's buffers: (layout, layout, in place)."""
+    from pyfft_amd import _native as N
+    batch, inplace = int(batch), bool(inplace)
+    p = plan._params
+    split = bool(p.split)
+    prec = "f64" if p.precision == N.F64 else "f32"
+    user = (split, split, inplace)
+    if not inplace and plan._runs_oop_nd(batch):
+        return {(("nd_oop", prec + ("_planes" if split else ""), int(p.x), int(p.y), int(p.z)), user)}
+    out = set()
+    descs = plan._descriptors(batch, inplace, False)
+    strat = plan._select_strategy(batch)
+    first = 0
+    if strat[0] == "fused2z":
+        pk = _persistent_key(plan)
+        out |= {(pk, user), (("plane_fused",) + pk[1:4], user)}
+        first = 2
+    elif strat[0] in plan.PERSISTENT:
+        return {(_persistent_key(plan), user)}
+    for key, i0, i1 in _chain_launches(plan, plan._kernels[first:], batch, first):
+        out.add((key, _unit_sides(plan, descs[i0], descs[i1], inplace)))
+    # (the several-work-groups instance of a one-launch plan's out-of-place executes: as keys_of_plan)
+    if not inplace and len(plan._kernels) == 1 and plan._kernels[0].kind == N.PASS_ND:
+        form = nd_kernel(descs[0], 0, small_launch=True, variant=0)
+        if form in (N.ND_KERNEL_ND2Z, N.ND_KERNEL_ND2ZP):
+            out.add((("nd2zp" if form == N.ND_KERNEL_ND2ZP else "nd2z", prec, int(p.x), int(p.y), int(p.z)), user))
+    return out
+
+
+def launch_sides_of(shape, dtype, batch, inplace):
+    """launch_sides_of_plan on the model of the full part"""
+    return launch_sides_of_plan(plan_for(shape, dtype), batch, inplace)
+
+
+PLACEMENTS = (False, True)        # in place?  (out of place first: where both produce a pair, the case runs the shorter contract)
+
+
 # pair kernels of the library that no default plan selects, only a development switch (MIFFT_DEBUG_PAIR = 2: the other y split of 256^3,
 # interleaved fp64); tests/test_pairs_gpu.py::test_pass_pairs_256_cubed_alternative_split runs it
 SWITCH_ONLY_PAIR_KEYS = {("pairXY", "f64", "interleaved", 256, 64, 4), ("pairYZ", "f64", "interleaved", 16384, 4, 256)}
@@ -267,56 +334,117 @@ AUDIT_MIN_BATCH = 3
 _audit = {}
 
 
-def audit_cases(max_log=MAX_LOG2_POINTS):
-    """[(shape, dtype name, batch, keys)]: for every key of universe() but SWITCH_ONLY_PAIR_KEYS, the smallest case (bytes per side) that
-    selects it with batch >= 3, in a batch that is no multiple of 4 where the key allows one (tiles that hold several transforms then end
-    partially filled); a case that is the smallest for several keys appears once, `keys` sorted.  Per (shape, dtype) the planner is asked
-    at batch 3 and at universe()'s batches; a key that only appears at a larger batch is bisected down to the batch where it appears.
-    A key without such a case raises (the audit must not silently lose an instance)."""
-    if max_log in _audit:
-        return list(_audit[max_log])
-    uni = universe(max_log)
-    want = set(uni) - SWITCH_ONLY_PAIR_KEYS
-    best = {}                       # key -> (bytes, order, shape, dtype, batch)
+def _smallest_cases(want, things_of, max_log, placements=(None,)):
+    """{thing: (bytes per side, order, shape, dtype name, batch, placement)}: for every member of `want` the smallest case (bytes per
+    side, then enumeration order) with batch >= 3 whose things_of(shape, dtype, batch, placement) holds it, in a batch that is no multiple
+    of 4 where the thing allows one (tiles that hold several transforms then end partially filled).  Per (shape, dtype, placement) the
+    planner is asked at batch 3 and at universe()'s batches; a thing that only appears at a larger batch is bisected down to the batch
+    where it appears."""
+    best = {}
     order = 0
     for shape in _shapes(max_log):
         for dtype in ALL_DTYPES:
             item = _item_bytes(shape, dtype)
-            memo = {}
-
-            def keys_at(b):
-                if b not in memo:
-                    memo[b] = set(k for k in keys_of(shape, dtype, b) if k in want)
-                return memo[b]
-
             probes = sorted(set([AUDIT_MIN_BATCH] + [max(AUDIT_MIN_BATCH, side // item) for side in UNIVERSE_SIDES]))
-            prev = None
-            for b in probes:
-                for k in keys_at(b):
-                    if (prev is not None and k in keys_at(prev)) or (k in best and best[k][0] <= AUDIT_MIN_BATCH * item):
-                        continue        # (recorded at the previous probe; or no batch of this shape beats the case found)
-                    lo, hi = prev, b
-                    while lo is not None and hi - lo > 1:
-                        mid = (lo + hi) // 2
-                        if k in keys_at(mid):
-                            hi = mid
-                        else:
-                            lo = mid
-                    if hi % 4 == 0 and k in keys_at(hi + 1):
-                        hi += 1
-                    order += 1
-                    cand = (hi * item, order, shape, numpy.dtype(dtype).name, hi)
-                    if k not in best or cand[0] < best[k][0]:
-                        best[k] = cand
-                prev = b
+            for placement in placements:
+                memo = {}
+
+                def at(b):
+                    if b not in memo:
+                        memo[b] = set(k for k in things_of(shape, dtype, b, placement) if k in want)
+                    return memo[b]
+
+                prev = None
+                for b in probes:
+                    for k in at(b):
+                        if (prev is not None and k in at(prev)) or (k in best and best[k][0] <= AUDIT_MIN_BATCH * item):
+                            continue        # (recorded at the previous probe; or no batch of this shape beats the case found)
+                        lo, hi = prev, b
+                        while lo is not None and hi - lo > 1:
+                            mid = (lo + hi) // 2
+                            if k in at(mid):
+                                hi = mid
+                            else:
+                                lo = mid
+                        if hi % 4 == 0 and k in at(hi + 1):
+                            hi += 1
+                        order += 1
+                        cand = (hi * item, order, shape, numpy.dtype(dtype).name, hi, placement)
+                        if k not in best or cand[0] < best[k][0]:
+                            best[k] = cand
+                    prev = b
+    return best
+
+
+def audit_cases(max_log=MAX_LOG2_POINTS):
+    """[(shape, dtype name, batch, keys)]: for every key of universe() but SWITCH_ONLY_PAIR_KEYS, the smallest case that selects it
+    (_smallest_cases); a case that is the smallest for several keys appears once, `keys` sorted.  A key without such a case raises (the
+    audit must not silently lose an instance)."""
+    if max_log in _audit:
+        return list(_audit[max_log])
+    uni = universe(max_log)
+    want = set(uni) - SWITCH_ONLY_PAIR_KEYS
+    best = _smallest_cases(want, lambda shape, dtype, b, _: keys_of(shape, dtype, b), max_log)
     missing = sorted(want - set(best), key=str)
     if missing:
         raise AssertionError("tests/kernel_coverage.py audit_cases: no case with batch >= %d selects %r" % (AUDIT_MIN_BATCH, missing[:40]))
     cases = {}
-    for k, (_, _, shape, dtname, batch) in best.items():
+    for k, (_, _, shape, dtname, batch, _) in best.items():
         cases.setdefault((shape, dtname, batch), []).append(k)
     out = sorted(((shape, dtname, batch, tuple(sorted(ks, key=str))) for (shape, dtname, batch), ks in cases.items()), key=lambda c: str(c[3][0]))
     _audit[max_log] = out
+    return list(out)
+
+
+# ---- one audit case per (key, sides) that audit_cases() leaves out (tests/test_instances_gpu.py::test_instance_sides) -----------------
+_sides_universe = {}
+_sides_audit = {}
+
+
+def sides_universe(max_log=MAX_LOG2_POINTS):
+    """{(key, sides): an example (shape, dtype name, batch, in place)} over universe()'s shapes and dtypes, at batch 3 and universe()'s
+    batches, in place and out of place"""
+    if max_log in _sides_universe:
+        return dict(_sides_universe[max_log])
+    out = {}
+    for shape in _shapes(max_log):
+        for dtype in ALL_DTYPES:
+            item = _item_bytes(shape, dtype)
+            for batch in sorted(set([AUDIT_MIN_BATCH] + [max(1, side // item) for side in UNIVERSE_SIDES])):
+                for inplace in PLACEMENTS:
+                    for pair in launch_sides_of(shape, dtype, batch, inplace):
+                        if pair not in out:
+                            out[pair] = (shape, numpy.dtype(dtype).name, batch, inplace)
+    _sides_universe[max_log] = out
+    return dict(out)
+
+
+def sides_of_cases(cases, placements=PLACEMENTS):
+    """{(key, sides)} the cases (shape, dtype name, batch, ...) launch on the model of the full part in the given placements"""
+    out = set()
+    for case in cases:
+        for inplace in placements:
+            out |= launch_sides_of(case[0], numpy.dtype(case[1]), case[2], inplace)
+    return out
+
+
+def sides_audit_cases(max_log=MAX_LOG2_POINTS):
+    """[(shape, dtype name, batch, in place, pairs)]: for every (key, sides) of sides_universe() that audit_cases() launches in neither
+    placement, the smallest case that launches it (_smallest_cases: out of place before in place); a case that is the smallest for
+    several pairs appears once, `pairs` sorted.  A pair without such a case raises."""
+    if max_log in _sides_audit:
+        return list(_sides_audit[max_log])
+    want = set(sides_universe(max_log)) - sides_of_cases(audit_cases(max_log))
+    best = _smallest_cases(want, launch_sides_of, max_log, PLACEMENTS)
+    missing = sorted(want - set(best), key=str)
+    if missing:
+        raise AssertionError("tests/kernel_coverage.py sides_audit_cases: no case with batch >= %d launches %r" % (AUDIT_MIN_BATCH, missing[:40]))
+    cases = {}
+    for pair, (_, _, shape, dtname, batch, inplace) in best.items():
+        cases.setdefault((shape, dtname, batch, inplace), []).append(pair)
+    out = sorted(((shape, dtname, batch, inplace, tuple(sorted(ps, key=str))) for (shape, dtname, batch, inplace), ps in cases.items()),
+                 key=lambda c: str(c[4][0]))
+    _sides_audit[max_log] = out
     return list(out)
 
 
@@ -484,6 +612,7 @@ REGISTRY = {
     },
     "test_instances_gpu": {
         "test_instance": lambda p: [_c(p["case"][0], numpy.dtype(p["case"][1]).type, p["case"][2])],
+        "test_instance_sides": lambda p: [_c(p["case"][0], numpy.dtype(p["case"][1]).type, p["case"][2])],
     },
     "test_extension_instances_gpu": {
         "test_extension_instance": None,     # (extension keys: extension_covered_keys)

@@ -26,6 +26,71 @@ def test_every_kernel_instance_a_default_plan_selects_has_a_default_gpu_test():
     assert not missing, "kernel instances no default-collected GPU test runs (key, an example plan): %r" % (missing[:40],)
 
 
+REGISTER_ONLY_LENGTHS = (4, 8, 16, 32)      # the lengths of the register-only strided kernel (mifft_colr_eligible)
+
+
+def _sides_run_by(test, case_of):
+    """{(key, sides)} the cases of a function of tests/test_instances_gpu.py launch, read off its parametrize mark; case_of(case) ->
+    (shape, dtype name, batch, the placements the test runs the contract in)"""
+    import test_instances_gpu as T
+    out = set()
+    for p in KC.params_of(getattr(T, test)):
+        shape, dtname, batch, placements = case_of(p["case"])
+        out |= KC.sides_of_cases([(shape, dtname, batch)], placements)
+    return out
+
+
+def test_every_kernel_runs_on_every_buffer_side_a_plan_gives_it():
+    """Every (key, sides) a default plan can launch -- which side holds split planes, whether the launch is aliased
+    (kernel_coverage.launch_sides_of_plan) -- runs under the per-instance contract: test_instance runs each of its cases out of place and
+    in place, test_instance_sides each case in the placement that produces its pairs."""
+    import test_instances_gpu as T
+    uni = KC.sides_universe()
+    run = _sides_run_by("test_instance", lambda c: (c[0], c[1], c[2], KC.PLACEMENTS))
+    if hasattr(T, "test_instance_sides"):         # (without it the rule fails below and names what nothing runs)
+        run |= _sides_run_by("test_instance_sides", lambda c: (c[0], c[1], c[2], (c[3],)))
+    # every key of universe() on at least one side (and the keys only a batch of 3 reaches: the chains of shapes whose big batches run
+    # persistent, fixed-shape plane kernels of small launches)
+    assert set(k for k, _ in uni) >= set(KC.universe())
+    # floors, about 5 % below the measured values: a planner or schedule change must not make the rule vacuous
+    one_side = [(k, s) for k, s in uni if s[0] != s[1]]
+    aliased = set(k for k, s in uni if s[2])
+    split_cols = {}
+    for k, s in uni:
+        if k[0] == "col" and k[2] == "split" and k[3] in REGISTER_ONLY_LENGTHS:
+            split_cols.setdefault((k[1], k[3]), set()).add(s[:2])
+    both_forms = sorted(pl for pl, forms in split_cols.items() if (False, False) in forms and any(planes_out for _, planes_out in forms))
+    assert len(uni) >= 1590, len(uni)                       # measured: 1676 pairs
+    assert len(one_side) >= 134, len(one_side)              # measured: 141 pairs with planes on exactly one side
+    assert len(aliased) >= 674, len(aliased)                # measured: 710 keys with an aliased launch
+    # measured: 4, the fp32 lengths (fp64 split plans take no detour through the interleaved temp buffer: their passes have planes on both sides)
+    assert set(both_forms) >= set(("f32", L) for L in REGISTER_ONLY_LENGTHS), both_forms
+    missing = sorted(((pair, ex) for pair, ex in uni.items() if pair not in run), key=str)
+    assert not missing, "%d (key, (planes in, planes out, aliased)) pairs no case of tests/test_instances_gpu.py launches (pair, an example " \
+        "(shape, dtype, batch, in place)): %r" % (len(missing), missing[:40])
+
+
+def test_no_pass_pair_is_scheduled_on_planes_it_cannot_take():
+    """The side between the two launches of a pair chain is interleaved (classify_pair, csrc/mifft_runtime.cpp): the library refuses a
+    (COL y, COL z) pair that reads split planes and a (ROW x, COL y) pair that writes them, so no default plan may schedule one (the
+    fp64 split plan of (256, 4, 16384): its row pass goes through the temp buffer, passes.yz_pair_chain)."""
+    bad = sorted(((k, s, ex) for (k, s), ex in KC.sides_universe().items() if (k[0] == "pairYZ" and s[0]) or (k[0] == "pairXY" and s[1])), key=str)
+    assert not bad, "pass pairs scheduled with split planes on their inner side (key, sides, an example): %r" % (bad,)
+
+
+def test_sides_cases_produce_their_pairs_and_nothing_the_key_cases_run():
+    run = KC.sides_of_cases(KC.audit_cases())
+    for shape, dtname, batch, inplace, pairs in KC.sides_audit_cases():
+        assert batch >= KC.AUDIT_MIN_BATCH
+        assert set(pairs) <= KC.launch_sides_of(shape, numpy.dtype(dtname), batch, inplace), (shape, dtname, batch, inplace)
+        assert not set(pairs) & run, (shape, dtname, batch, inplace)
+    # both placements of an execute together launch exactly the keys of keys_of(): a side is a property of a key's launch, no key of its own
+    for shape, dtname, batch, _ in KC.audit_cases():
+        dt = numpy.dtype(dtname)
+        keys = set(k for inplace in KC.PLACEMENTS for k, _ in KC.launch_sides_of(shape, dt, batch, inplace))
+        assert keys == set(k for k in KC.keys_of(shape, dt, batch) if k is not None), (shape, dtname, batch)
+
+
 def test_pair_kernel_table_and_reachable_pair_keys_agree():
     """mifft_pair_kernel_supported over its key space (include/mifft.h): every pair key a plan reaches has a kernel, and every kernel of
     the table is reached by some default plan -- no dead instance, no plan that would ask for a missing one."""
