@@ -1,26 +1,15 @@
 // f64 one-launch convolution rows (fft_conv_row.hpp): complex rows of L points and real rows of n = 2L reals, one instance per
-// (complex / real, L); correlation and the spectrum pitch are run-time arguments.  The work-group shapes and forward radix lists are those
-// of the real rows of L packed points (fft_real_row_f64.hip), so the LDS footprint matches the row kernels of L points.
+// (complex / real, L); correlation and the spectrum pitch are run-time arguments.  Work-group shapes and forward radix lists:
+// fft_row_shapes.hpp, so the LDS footprint matches the row kernels of L points.
 #include "mifft_internal.h"
 #include "fft_conv_row.hpp"
 extern "C" int mifft_conv_row_dispatch_f64(int real, int L, const mifft::ConvRowArgs* a, hipStream_t s, int query_only) {
     using namespace mifft;
-    switch (L) {
-        case 2: return launch_conv_row_small<double, 2>(real, a, s, query_only);
-        case 4: return launch_conv_row_small<double, 4>(real, a, s, query_only);
-        case 8: return launch_conv_row_small<double, 8>(real, a, s, query_only);
-        case 16: return launch_conv_row_small<double, 16>(real, a, s, query_only);
-        case 32: return launch_conv_row_small<double, 32>(real, a, s, query_only);
-        case 64: return launch_conv_row<double, 64, 32, 256, RadixList<8, 8>>(real, a, s, query_only);
-        case 128: return launch_conv_row<double, 128, 32, 256, RadixList<16, 8>>(real, a, s, query_only);
-        case 256: return launch_conv_row<double, 256, 8, 256, RadixList<8, 8, 4>>(real, a, s, query_only);
-        case 512: return launch_conv_row<double, 512, 8, 256, RadixList<16, 2, 16>>(real, a, s, query_only);
-        case 1024: return launch_conv_row<double, 1024, 4, 256, RadixList<16, 4, 16>>(real, a, s, query_only);
-        case 2048: return launch_conv_row<double, 2048, 1, 128, RadixList<16, 8, 16>>(real, a, s, query_only);
-        case 4096: return launch_conv_row<double, 4096, 1, 256, RadixList<16, 16, 16>>(real, a, s, query_only);
-        // real rows of 16384 and 32768 reals spill (308 / 836 bytes of scratch against 0 / 168 for the real rows), and so does the
-        // complex row of 16384 points (272 against 0): those run the composed form (docs/extensions.md "Convolution plans")
-        case 8192: return real ? -2 : launch_conv_row<double, 8192, 1, 512, RadixList<2, 16, 16, 16>, true>(real, a, s, query_only);
-    }
-    return -2;
+    int rc = -2;
+    // real rows of 16384 and 32768 reals spill (308 / 836 bytes of scratch against 0 / 168 for the real rows), and so does the
+    // complex row of 16384 points (272 against 0): those run the composed form (docs/extensions.md "Convolution plans")
+    for_length<2, 4, 8, 16, 32>(L, rc, [&](auto l) { return launch_conv_row_small<double, l>(real, a, s, query_only); }) ||
+        for_length<64, 128, 256, 512, 1024, 2048, 4096>(L, rc, [&](auto l) { return launch_conv_row<double, l>(real, a, s, query_only); }) ||
+        for_length<8192>(L, rc, [&](auto l) { return real ? -2 : launch_conv_row<double, l>(real, a, s, query_only); });
+    return rc;
 }

@@ -14,9 +14,7 @@
 //            the pair the packing identity needs, so no second exchange.  Index 0 takes X[0] and X[L] through their real parts (the
 //            edge rule of real_row_inv_kernel, numpy's irfft).  The inverse L-point stages store the n reals.
 // Rows of L <= 32 (complex or packed points): one thread per row, both transforms in registers (Dft<L>), as real_row_small_kernel.
-// Work-group shapes and forward radix lists are those of the real rows of L packed points (fft_real_row_f32.hip / _f64.hip): the complex
-// row instances of L >= 256 points, and the register-edged form for L = 64, 128 too (the complex ROW dispatch runs the LDS-staged tile
-// kernel there, which has no register epilogue).
+// Work-group shapes and forward radix lists: Row2Shape (fft_row_shapes.hpp), as for the real rows of L packed points.
 #pragma once
 #include <type_traits>
 #include "fft_real_row.hpp"
@@ -212,9 +210,8 @@ __device__ __forceinline__ void conv_row_body(const ConvRowArgs& a) {
         const T sc = (T)a.scale;
         static_for<L>([&](auto k) { out[k] = cplx<T>{v[k].x * sc, -v[k].y * sc}; });
     } else {
-        constexpr int PPT = L / TPR;
-        constexpr int LP = L + L / 16;
-        static_assert(TPR * W == NT && PPT * TPR == L && L >= 16, "bad row configuration");
+        using G = Row2Geom<L, W, NT>;
+        constexpr int PPT = G::PPT, LP = G::LP;
         using LdsT = typename std::conditional<HALF, T, cplx<T>>::type;
         __shared__ __attribute__((aligned(16))) LdsT lds[W * LP];
         const int c = W == 1 ? 0 : threadIdx.x / TPR, u = W == 1 ? threadIdx.x : threadIdx.x % TPR;
@@ -246,21 +243,18 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(OCC))) 
 }
 
 // real != 0: L packed points (n = 2L reals); 0 launched (query: a kernel exists), -2 none, -1 grid too large
-template <typename T, int L, int W, int NT, typename RL, bool HALF = false, int OCC = 1>
+template <typename T, int L, typename S = Row2Shape<T, L>>
 static inline int launch_conv_row(int real, const ConvRowArgs* a, hipStream_t s, int query_only) {
-    if (query_only) return 0;
-    const long long tiles = (a->rows + W - 1) / W;
-    if (tiles <= 0) return 0;
-    if (tiles > 2147483647ll) return -1;
-    if (real) hipLaunchKernelGGL((conv_row_real_kernel<T, L, W, NT, HALF, OCC, RL>), dim3((unsigned)tiles), dim3(NT), 0, s, *a);
-    else hipLaunchKernelGGL((conv_row_kernel<T, L, W, NT, HALF, OCC, RL>), dim3((unsigned)tiles), dim3(NT), 0, s, *a);
-    return (int)hipGetLastError();
+    return launch_groups(a, &ConvRowArgs::rows, S::W, query_only, [&](dim3 grid) {
+        if (real) hipLaunchKernelGGL((conv_row_real_kernel<T, L, S::W, S::NT, S::HALF, S::OCC, typename S::RL>), grid, dim3(S::NT), 0, s, *a);
+        else hipLaunchKernelGGL((conv_row_kernel<T, L, S::W, S::NT, S::HALF, S::OCC, typename S::RL>), grid, dim3(S::NT), 0, s, *a);
+    });
 }
 
 // L <= 32: one thread per row
 template <typename T, int L>
 static inline int launch_conv_row_small(int real, const ConvRowArgs* a, hipStream_t s, int query_only) {
-    return launch_conv_row<T, L, 256, 256, RadixList<L>>(real, a, s, query_only);
+    return launch_conv_row<T, L, Row2ShapeOf<256, 256, RadixList<L>>>(real, a, s, query_only);
 }
 
 }  // namespace mifft

@@ -17,21 +17,15 @@
 
 namespace mifft {
 
-// row configuration of the x axis (the plain launch's: fft_row_f32.hip): rows per group, threads per row = 256 / W, radix list
-template <int NX> struct Fused2rRow;
-template <> struct Fused2rRow<256> { static constexpr int W = 8; using RL = RadixList<8, 8, 4>; };
-template <> struct Fused2rRow<512> { static constexpr int W = 8; using RL = RadixList<16, 2, 16>; };
-template <> struct Fused2rRow<1024> { static constexpr int W = 4; using RL = RadixList<16, 4, 16>; };
-template <typename RL> struct Fused2rFirst;
-template <int R, int... Rest> struct Fused2rFirst<RadixList<R, Rest...>> { static constexpr int value = R; };
-
 // AY = ny / 256, NX = nx: fp32, split-complex user planes, interleaved ring
 template <int NX, int AY>
 __global__ void __launch_bounds__(256, 2) fft_fused2r_kernel(const FusedArgs f) {
     using T = float;
-    using Row = Fused2rRow<NX>;
-    constexpr int NY = 256 * AY, W = Row::W, TPR = 256 / W, PPT = NX / TPR, LP = NX + NX / 16;
-    constexpr int R = Fused2rFirst<typename Row::RL>::value, LR = NX / R;
+    using Row = Row2Shape<T, NX>;       // the x axis in the plain launch's shape (fft_row_shapes.hpp)
+    using G = Row2Geom<NX, Row::W, Row::NT>;
+    static_assert(Row::NT == 256 && !Row::HALF, "pass 0 runs the row's shape on this kernel's 256 threads, full-width exchange");
+    constexpr int NY = 256 * AY, W = Row::W, TPR = G::TPR, PPT = G::PPT, LP = G::LP;
+    constexpr int R = FirstRadix<typename Row::RL>::value, LR = NX / R;
     using Stages = Row2Stages<T, NX, TPR, 1, true, false, typename Row::RL>;
     constexpr int E0 = W * LP, E1 = Col2Lds<AY, false, sizeof(cplx<T>)>::ELEMS;
     __shared__ __attribute__((aligned(16))) cplx<T> lds[E0 > E1 ? E0 : E1];

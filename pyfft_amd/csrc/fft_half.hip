@@ -10,35 +10,21 @@ namespace {
 using C32 = mifft::Complex32<float>;
 
 template <int P, int NT> int launch_nd(const mifft::NdArgs* a, hipStream_t s) {
-    const long long tiles = (a->total + P - 1) / P;
-    if (tiles <= 0) return 0;
-    if (tiles > 2147483647ll) return -1;
-    hipLaunchKernelGGL((mifft::fft_nd_kernel<C32, P, NT>), dim3((unsigned)tiles), dim3(NT), 0, s, *a);
-    return (int)hipGetLastError();
+    return mifft::launch_groups(a, &mifft::NdArgs::total, P, 0, [&](dim3 grid) {
+        hipLaunchKernelGGL((mifft::fft_nd_kernel<C32, P, NT>), grid, dim3(NT), 0, s, *a);
+    });
 }
 }  // namespace
 
-// Rows of L points, interleaved both sides: the configurations of mifft_dispatch_row_f32's interleaved kernels -- register-edged
-// (fft_row2.hpp) for L >= 256, LDS-staged ROW tiles (fft_tile.hpp) below.  0 launched (query: a kernel exists), -2 none, -1 grid
-// too large
+// Rows of L points, interleaved both sides: the lengths of mifft_dispatch_row_f32's interleaved kernels -- register-edged (fft_row2.hpp,
+// float's shapes of fft_row_shapes.hpp) for L >= 256, the fp32 LDS-staged ROW tiles (fft_tile.hpp) below.  0 launched (query: a kernel
+// exists), -2 none, -1 grid too large
 extern "C" int mifft_c32_row_dispatch(int L, const mifft::TileArgs* a, hipStream_t s, int query_only) {
     using namespace mifft;
+    int rc;
+    if (for_length<256, 512, 1024, 2048, 4096, 8192, 16384, 32768>(L, rc, [&](auto l) { return launch_row2<C32, l>(a, s, query_only); })) return rc;
     switch (L) {
-        case 32768: return launch_row2<C32, 32768, 1, 1024, RadixList<32, 32, 32>, true, 4>(a, s, query_only);
-        case 16384: return launch_row2<C32, 16384, 1, 512, RadixList<4, 16, 16, 16>, true, 4>(a, s, query_only);
-        case 8192: return launch_row2<C32, 8192, 1, 256, RadixList<16, 16, 32>, true>(a, s, query_only);
-        case 4096: return launch_row2<C32, 4096, 1, 256, RadixList<16, 16, 16>>(a, s, query_only);
-        case 2048: return launch_row2<C32, 2048, 1, 128, RadixList<16, 8, 16>>(a, s, query_only);
-        case 1024: return launch_row2<C32, 1024, 4, 256, RadixList<16, 4, 16>>(a, s, query_only);
-        case 512: return launch_row2<C32, 512, 8, 256, RadixList<16, 2, 16>>(a, s, query_only);
-        case 256: return launch_row2<C32, 256, 8, 256, RadixList<8, 8, 4>>(a, s, query_only);
-        MIFFT_ROW_CASE(C32, 2, 2048, 256, 2)
-        MIFFT_ROW_CASE(C32, 4, 1024, 256, 4)
-        MIFFT_ROW_CASE(C32, 8, 512, 256, 8)
-        MIFFT_ROW_CASE(C32, 16, 256, 256, 16)
-        MIFFT_ROW_CASE(C32, 32, 128, 256, 8, 4)
-        MIFFT_ROW_CASE(C32, 64, 64, 256, 8, 8)
-        MIFFT_ROW_CASE(C32, 128, 32, 256, 16, 8)
+        MIFFT_ROW_CASES_F32_SHORT(C32)
     }
     return -2;
 }

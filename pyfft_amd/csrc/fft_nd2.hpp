@@ -334,8 +334,6 @@ template <int L, int MAXR, bool REM_FIRST> struct AutoRadix {
     using type = typename std::conditional<REM_FIRST, typename RadixCat<Rem, Full>::type,
                                            typename RadixCat<Full, Rem>::type>::type;
 };
-template <typename RL> struct RadixFirst { static constexpr int value = 1; };
-template <int R, int... Rest> struct RadixFirst<RadixList<R, Rest...>> { static constexpr int value = R; };
 
 // Tile and launch shape for an (X, Y, Z) transform of type T: the smallest tile of 1 / 2 / 4 / 8 x TILE0 points that holds
 // one transform (TILE0 = 4096 points fp32, 2048 fp64: 32 KiB of LDS, four work-groups per CU).  4 x TILE0 ("big") runs in
@@ -371,7 +369,7 @@ template <typename T, int X, int Y, int Z> struct Nd2Auto {
     using RLY = typename std::conditional<(R32 && Y == 32), RadixList<32>, typename AutoRadix<Y, MAXR, YF>::type>::type;
     using RLZ = typename std::conditional<(R32 && Z == 32), RadixList<32>, typename AutoRadix<Z, MAXR, false>::type>::type;
     // the first stage reads runs of (X / first radix) points: straight from HBM when that is >= 128 bytes
-    static constexpr bool EDGE_IN = HALF || (X > 1 && (X / RadixFirst<RLX>::value) * (int)sizeof(cplx<T>) >= 128);
+    static constexpr bool EDGE_IN = HALF || (X > 1 && (X / FirstRadix<RLX>::value) * (int)sizeof(cplx<T>) >= 128);
 };
 
 // the complex32-storage twin of launch_nd2_auto's kernel: the same configuration (Nd2Auto<T, ...>)

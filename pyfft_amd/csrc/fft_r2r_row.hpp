@@ -115,12 +115,11 @@ template <typename T, int L> struct R2rInvEpi {
 
 template <typename T, int L, int W, int NT, int OCC, typename RL>
 __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(OCC))) r2r_row_fwd_kernel(const TileArgs a) {
-    constexpr int TPR = NT / W;
-    constexpr int PPT = L / TPR;
-    constexpr int LP = L + L / 16;
+    using G = Row2Geom<L, W, NT>;
+    constexpr int TPR = G::TPR, PPT = G::PPT, LP = G::LP;
     constexpr int R0 = FirstRadix<RL>::value;
     constexpr int LR0 = L / R0;
-    static_assert(TPR * W == NT && PPT * TPR == L && L >= 16 && PPT % 2 == 0, "bad row configuration");
+    static_assert(PPT % 2 == 0, "the load prologue / store epilogue moves four reals per step");
     __shared__ __attribute__((aligned(16))) cplx<T> lds[W * LP];
     const int c = W == 1 ? 0 : threadIdx.x / TPR, u = W == 1 ? threadIdx.x : threadIdx.x % TPR;
     const long long row = (long long)blockIdx.x * W + c;
@@ -149,12 +148,11 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(OCC))) 
 
 template <typename T, int L, int W, int NT, int OCC, typename RL>
 __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(OCC))) r2r_row_inv_kernel(const TileArgs a) {
-    constexpr int TPR = NT / W;
-    constexpr int PPT = L / TPR;
-    constexpr int LP = L + L / 16;
+    using G = Row2Geom<L, W, NT>;
+    constexpr int TPR = G::TPR, PPT = G::PPT, LP = G::LP;
     constexpr int R0 = FirstRadix<RL>::value;
     constexpr int LR0 = L / R0;
-    static_assert(TPR * W == NT && PPT * TPR == L && L >= 16 && PPT % 2 == 0, "bad row configuration");
+    static_assert(PPT % 2 == 0, "the load prologue / store epilogue moves four reals per step");
     __shared__ __attribute__((aligned(16))) cplx<T> lds[W * LP];
     const int c = W == 1 ? 0 : threadIdx.x / TPR, u = W == 1 ? threadIdx.x : threadIdx.x % TPR;
     const long long row = (long long)blockIdx.x * W + c;
@@ -219,26 +217,23 @@ __global__ void __launch_bounds__(256) r2r_row_small_kernel(const TileArgs a) {
     }
 }
 
-template <typename T, int L, int W, int NT, typename RL, int OCC = 1>
+// (the kernels exchange full complex numbers: a length whose Row2Shape is HALF has no r2r row)
+template <typename T, int L>
 static inline int launch_r2r_row(const TileArgs* a, int inverse, hipStream_t s, int query_only) {
-    if (query_only) return 0;
-    const long long tiles = (a->total + W - 1) / W;
-    if (tiles <= 0) return 0;
-    if (tiles > 2147483647ll) return -1;
-    if (inverse) hipLaunchKernelGGL((r2r_row_inv_kernel<T, L, W, NT, OCC, RL>), dim3((unsigned)tiles), dim3(NT), 0, s, *a);
-    else hipLaunchKernelGGL((r2r_row_fwd_kernel<T, L, W, NT, OCC, RL>), dim3((unsigned)tiles), dim3(NT), 0, s, *a);
-    return (int)hipGetLastError();
+    using S = Row2Shape<T, L>;
+    static_assert(!S::HALF, "r2r rows have no half-width exchange");
+    return launch_groups(a, &TileArgs::total, S::W, query_only, [&](dim3 grid) {
+        if (inverse) hipLaunchKernelGGL((r2r_row_inv_kernel<T, L, S::W, S::NT, S::OCC, typename S::RL>), grid, dim3(S::NT), 0, s, *a);
+        else hipLaunchKernelGGL((r2r_row_fwd_kernel<T, L, S::W, S::NT, S::OCC, typename S::RL>), grid, dim3(S::NT), 0, s, *a);
+    });
 }
 
 template <typename T, int L>
 static inline int launch_r2r_row_small(const TileArgs* a, int inverse, hipStream_t s, int query_only) {
-    if (query_only) return 0;
-    const long long blocks = (a->total + 255) / 256;
-    if (blocks <= 0) return 0;
-    if (blocks > 2147483647ll) return -1;
-    if (inverse) hipLaunchKernelGGL((r2r_row_small_kernel<T, L, true>), dim3((unsigned)blocks), dim3(256), 0, s, *a);
-    else hipLaunchKernelGGL((r2r_row_small_kernel<T, L, false>), dim3((unsigned)blocks), dim3(256), 0, s, *a);
-    return (int)hipGetLastError();
+    return launch_groups(a, &TileArgs::total, 256, query_only, [&](dim3 grid) {
+        if (inverse) hipLaunchKernelGGL((r2r_row_small_kernel<T, L, true>), grid, dim3(256), 0, s, *a);
+        else hipLaunchKernelGGL((r2r_row_small_kernel<T, L, false>), grid, dim3(256), 0, s, *a);
+    });
 }
 
 }  // namespace mifft

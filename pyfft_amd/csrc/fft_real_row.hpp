@@ -1,7 +1,7 @@
 // One-launch real-input rows (Plan(n, real=True) for 4 <= n <= 65536 fp32 / 32768 fp64): the row transform of the L = n / 2 packed
 // points z[m] = x[2m] + i x[2m + 1] and the separation into the half spectrum (csrc/fft_real.hip states the identity) in ONE
 // work-group, so that a row crosses HBM once: n s bytes in, (L + 1) 2s bytes out (s the scalar size).
-//   forward  the stages of fft_row2.hpp (same work-group shapes, LDS and occupancy as the complex row of L points); instead of the
+//   forward  the stages of fft_row2.hpp (Row2Shape of fft_row_shapes.hpp: the complex row's work-group shape, LDS and occupancy); instead of the
 //            last stage's stores, RealSepEpi exchanges the transform through the row's LDS slab once more (each point needs its mirror
 //            Z[L - k], held by another thread) and stores X[k], k < L, plus X[L] from the thread that holds Z[0]
 //   inverse  every thread loads the half-spectrum points its first stage needs and their mirrors X[L - k] (the same row read
@@ -14,9 +14,6 @@
 #include "fft_row2.hpp"
 
 namespace mifft {
-
-template <typename RL> struct FirstRadix;
-template <int R, int... Rs> struct FirstRadix<RadixList<R, Rs...>> { static constexpr int value = R; };
 
 // X[k] = 1/2 (s - i w(n)^k d), s = Z[k] + conj Z[L - k], d = Z[k] - conj Z[L - k]; h = scale / 2
 template <typename T> __device__ __forceinline__ cplx<T> real_sep(cplx<T> s, cplx<T> d, cplx<T> w, T h) {
@@ -95,10 +92,8 @@ template <typename T, int L, bool HALF> struct RealSepEpi {
 // ---- forward: W rows of L packed points per work-group (the complex row's shape) -------------------------------------------------
 template <typename T, int L, int W, int NT, bool HALF, int OCC, typename RL>
 __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(OCC))) real_row_fwd_kernel(const TileArgs a) {
-    constexpr int TPR = NT / W;
-    constexpr int PPT = L / TPR;
-    constexpr int LP = L + L / 16;
-    static_assert(TPR * W == NT && PPT * TPR == L && L >= 16, "bad row configuration");
+    using G = Row2Geom<L, W, NT>;
+    constexpr int TPR = G::TPR, PPT = G::PPT, LP = G::LP;
     using LdsT = typename std::conditional<HALF, T, cplx<T>>::type;
     __shared__ __attribute__((aligned(16))) LdsT lds[W * LP];
     const int c = W == 1 ? 0 : threadIdx.x / TPR, u = W == 1 ? threadIdx.x : threadIdx.x % TPR;
@@ -118,12 +113,10 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(OCC))) 
 // ---- inverse: pack in registers, then the inverse L-point stages store the n reals ------------------------------------------------
 template <typename T, int L, int W, int NT, bool HALF, int OCC, typename RL>
 __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(OCC))) real_row_inv_kernel(const TileArgs a) {
-    constexpr int TPR = NT / W;
-    constexpr int PPT = L / TPR;
-    constexpr int LP = L + L / 16;
+    using G = Row2Geom<L, W, NT>;
+    constexpr int TPR = G::TPR, PPT = G::PPT, LP = G::LP;
     constexpr int R0 = FirstRadix<RL>::value;
     constexpr int LR0 = L / R0;
-    static_assert(TPR * W == NT && PPT * TPR == L && L >= 16, "bad row configuration");
     using LdsT = typename std::conditional<HALF, T, cplx<T>>::type;
     __shared__ __attribute__((aligned(16))) LdsT lds[W * LP];
     const int c = W == 1 ? 0 : threadIdx.x / TPR, u = W == 1 ? threadIdx.x : threadIdx.x % TPR;
@@ -206,26 +199,21 @@ __global__ void __launch_bounds__(256) real_row_small_kernel(const TileArgs a) {
     }
 }
 
-template <typename T, int L, int W, int NT, typename RL, bool HALF = false, int OCC = 1>
+template <typename T, int L>
 static inline int launch_real_row(const TileArgs* a, int inverse, hipStream_t s, int query_only) {
-    if (query_only) return 0;
-    const long long tiles = (a->total + W - 1) / W;
-    if (tiles <= 0) return 0;
-    if (tiles > 2147483647ll) return -1;
-    if (inverse) hipLaunchKernelGGL((real_row_inv_kernel<T, L, W, NT, HALF, OCC, RL>), dim3((unsigned)tiles), dim3(NT), 0, s, *a);
-    else hipLaunchKernelGGL((real_row_fwd_kernel<T, L, W, NT, HALF, OCC, RL>), dim3((unsigned)tiles), dim3(NT), 0, s, *a);
-    return (int)hipGetLastError();
+    using S = Row2Shape<T, L>;
+    return launch_groups(a, &TileArgs::total, S::W, query_only, [&](dim3 grid) {
+        if (inverse) hipLaunchKernelGGL((real_row_inv_kernel<T, L, S::W, S::NT, S::HALF, S::OCC, typename S::RL>), grid, dim3(S::NT), 0, s, *a);
+        else hipLaunchKernelGGL((real_row_fwd_kernel<T, L, S::W, S::NT, S::HALF, S::OCC, typename S::RL>), grid, dim3(S::NT), 0, s, *a);
+    });
 }
 
 template <typename T, int L>
 static inline int launch_real_row_small(const TileArgs* a, int inverse, hipStream_t s, int query_only) {
-    if (query_only) return 0;
-    const long long blocks = (a->total + 255) / 256;
-    if (blocks <= 0) return 0;
-    if (blocks > 2147483647ll) return -1;
-    if (inverse) hipLaunchKernelGGL((real_row_small_kernel<T, L, true>), dim3((unsigned)blocks), dim3(256), 0, s, *a);
-    else hipLaunchKernelGGL((real_row_small_kernel<T, L, false>), dim3((unsigned)blocks), dim3(256), 0, s, *a);
-    return (int)hipGetLastError();
+    return launch_groups(a, &TileArgs::total, 256, query_only, [&](dim3 grid) {
+        if (inverse) hipLaunchKernelGGL((real_row_small_kernel<T, L, true>), grid, dim3(256), 0, s, *a);
+        else hipLaunchKernelGGL((real_row_small_kernel<T, L, false>), grid, dim3(256), 0, s, *a);
+    });
 }
 
 }  // namespace mifft

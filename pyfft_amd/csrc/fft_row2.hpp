@@ -12,6 +12,7 @@
 #pragma once
 #include <type_traits>
 #include "fft_tile.hpp"
+#include "fft_row_shapes.hpp"
 
 namespace mifft {
 
@@ -267,16 +268,22 @@ struct Row2Stages<T, L, TPR, Ns, FIRST, HALF, RadixList<R, Rest...>, LAY, EPI, S
     }
 };
 
+// What the row kernels derive from (L, W, NT): TPR threads per row, PPT points per thread, LP = a row's padded LDS slab (row2_pad)
+template <int L, int W, int NT> struct Row2Geom {
+    static constexpr int TPR = NT / W;
+    static constexpr int PPT = L / TPR;
+    static constexpr int LP = L + L / 16;
+    static_assert(TPR * W == NT && PPT * TPR == L && L >= 16, "bad row configuration");
+};
+
 // OCC: waves per SIMD the register allocation must leave room for (1 = whatever the kernel needs)
 // TS = Complex32<T> (fft_tile.hpp): complex32 storage, interleaved (LAY 0), plain accesses
 template <typename TS, int L, int W, int NT, bool HALF, int OCC, typename RL, int LAY = 0>
 __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(OCC))) fft_row2_kernel(const TileArgs a) {
     using T = typename StorageOf<TS>::work;
     using ST = typename StorageOf<TS>::store;
-    constexpr int TPR = NT / W;
-    constexpr int PPT = L / TPR;
-    constexpr int LP = L + L / 16;
-    static_assert(TPR * W == NT && PPT * TPR == L && L >= 16, "bad row configuration");
+    using G = Row2Geom<L, W, NT>;
+    constexpr int TPR = G::TPR, PPT = G::PPT, LP = G::LP;
     using LdsT = typename std::conditional<HALF, T, cplx<T>>::type;
     __shared__ __attribute__((aligned(16))) LdsT lds[W * LP];
     const int c = W == 1 ? 0 : threadIdx.x / TPR, u = W == 1 ? threadIdx.x : threadIdx.x % TPR;
@@ -301,23 +308,22 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(OCC))) 
     Row2Stages<T, L, TPR, 1, true, HALF, RL, LAY, void, ST>::run(lds + c * LP, v, a, u, inb, outb, voff, valid, nullptr, false, inb1, outb1);
 }
 
-template <typename T, int L, int W, int NT, typename RL, bool HALF = false, int OCC = 1, int LAY = 0>
+// TS, L: the shape is Row2Shape's (fft_row_shapes.hpp) for the working precision of TS
+template <typename TS, int L, int LAY = 0>
 static inline int launch_row2(const TileArgs* a, hipStream_t s, int query_only) {
-    if (query_only) return 0;
-    const long long tiles = (a->total + W - 1) / W;
-    if (tiles <= 0) return 0;
-    if (tiles > 2147483647ll) return -1;
-    hipLaunchKernelGGL((fft_row2_kernel<T, L, W, NT, HALF, OCC, RL, LAY>), dim3((unsigned)tiles), dim3(NT), 0, s, *a);
-    return (int)hipGetLastError();
+    using S = Row2Shape<typename StorageOf<TS>::work, L>;
+    return launch_groups(a, &TileArgs::total, S::W, query_only, [&](dim3 grid) {
+        hipLaunchKernelGGL((fft_row2_kernel<TS, L, S::W, S::NT, S::HALF, S::OCC, typename S::RL, LAY>), grid, dim3(S::NT), 0, s, *a);
+    });
 }
 
 // the same configuration for the layout of the pass at hand: interleaved, planes -> planes (a split-complex single-pass plan), planes
 // -> interleaved (the first pass of a split-complex multi-pass plan, whose temp buffer is interleaved)
-template <typename T, int L, int W, int NT, typename RL, bool HALF = false, int OCC = 1>
+template <typename T, int L>
 static inline int launch_row2_lay(const TileArgs* a, hipStream_t s, int query_only) {
-    if (query_only || (!a->split && !a->split_out)) return launch_row2<T, L, W, NT, RL, HALF, OCC, 0>(a, s, query_only);
-    if (a->split && a->split_out) return launch_row2<T, L, W, NT, RL, HALF, OCC, 3>(a, s, 0);
-    if (a->split) return launch_row2<T, L, W, NT, RL, HALF, OCC, 1>(a, s, 0);
+    if (query_only || (!a->split && !a->split_out)) return launch_row2<T, L, 0>(a, s, query_only);
+    if (a->split && a->split_out) return launch_row2<T, L, 3>(a, s, 0);
+    if (a->split) return launch_row2<T, L, 1>(a, s, 0);
     return -2;      // (interleaved -> planes: no plan has a contiguous-axis pass last but one; the LDS-staged kernel takes it)
 }
 

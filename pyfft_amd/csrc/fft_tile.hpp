@@ -43,6 +43,22 @@ struct TileArgs {
 };
 
 template <int... Rs> struct RadixList {};
+// the first radix of a list; 1 for the empty list (an axis of one point has no stage)
+template <typename RL> struct FirstRadix { static constexpr int value = 1; };
+template <int R, int... Rs> struct FirstRadix<RadixList<R, Rs...>> { static constexpr int value = R; };
+
+// The launchers' grid arithmetic and return codes: one work-group per `per_group` of the a->*items items.  A query returns 0 before
+// `a` is read (the *_supported entry points pass a null pointer); nothing to do returns 0 without a launch; a grid beyond 2^31 - 1
+// work-groups returns -1; otherwise launch(grid) enqueues the kernel and the launch's hipError_t is returned.
+template <typename Args, typename Launch>
+static inline int launch_groups(const Args* a, long long Args::*items, int per_group, int query_only, Launch&& launch) {
+    if (query_only) return 0;
+    const long long groups = (a->*items + per_group - 1) / per_group;
+    if (groups <= 0) return 0;
+    if (groups > 2147483647ll) return -1;
+    launch(dim3((unsigned)groups));
+    return (int)hipGetLastError();
+}
 
 // Storage type ST of a kernel's HBM side: T (the default: memory holds cplx<T>, the working type) or _Float16 (complex32: one fp16
 // real and one fp16 imaginary part per point, docs/extensions.md "Half-precision transforms").  Only the first stage's loads and the

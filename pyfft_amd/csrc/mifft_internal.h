@@ -97,12 +97,9 @@ int mifft_nd2_c32_launch(int x, int y, int z, const mifft::TileArgs* a, hipStrea
 namespace mifft {
 template <typename T, int L, int W, int NT, bool ROW, bool TR, typename RL>
 static inline int launch_tile(const TileArgs* a, hipStream_t s, int query_only) {
-    if (query_only) return 0;
-    const long long tiles = (a->total + W - 1) / W;
-    if (tiles <= 0) return 0;
-    if (tiles > 2147483647ll) return -1;
-    hipLaunchKernelGGL((fft_tile_kernel<T, L, W, NT, ROW, TR, RL>), dim3((unsigned)tiles), dim3(NT), 0, s, *a);
-    return (int)hipGetLastError();
+    return launch_groups(a, &TileArgs::total, W, query_only, [&](dim3 grid) {
+        hipLaunchKernelGGL((fft_tile_kernel<T, L, W, NT, ROW, TR, RL>), grid, dim3(NT), 0, s, *a);
+    });
 }
 }  // namespace mifft
 
@@ -113,3 +110,12 @@ static inline int launch_tile(const TileArgs* a, hipStream_t s, int query_only) 
 #define MIFFT_ROW_CASE(T, Lv, Wv, NTv, ...)                                                             \
     case Lv:                                                                                            \
         return mifft::launch_tile<T, Lv, Wv, NTv, true, false, mifft::RadixList<__VA_ARGS__>>(a, s, query_only);
+// the fp32 ROW tiles below the register-edged rows (L < 256): fft_row_f32.hip expands them for float, fft_half.hip for Complex32<float>
+#define MIFFT_ROW_CASES_F32_SHORT(T)       \
+    MIFFT_ROW_CASE(T, 2, 2048, 256, 2)     \
+    MIFFT_ROW_CASE(T, 4, 1024, 256, 4)     \
+    MIFFT_ROW_CASE(T, 8, 512, 256, 8)      \
+    MIFFT_ROW_CASE(T, 16, 256, 256, 16)    \
+    MIFFT_ROW_CASE(T, 32, 128, 256, 8, 4)  \
+    MIFFT_ROW_CASE(T, 64, 64, 256, 8, 8)   \
+    MIFFT_ROW_CASE(T, 128, 32, 256, 16, 8)

@@ -862,6 +862,30 @@ def test_nd_kernel_snapshot():
     assert count["nd"] > 100000 and count["refused"] > 100000 and sum(seen.values()) + count["nd"] + count["refused"] == 1404000
 
 
+def test_row_supported_snapshot():
+    """The row families (complex, complex32, real, convolution, cosine / sine) take their work-group shapes from one table
+    (csrc/fft_row_shapes.hpp) and name their lengths in per-family lists.  Which lengths each has a kernel for is what the library
+    answered when every family spelt its instances out: tests/golden/row_supported_snapshot.json, written from that library (see
+    make_row_supported_snapshot.py) for both precisions and every power of two from 2 to 2^18."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    import make_row_supported_snapshot as snap
+    from pyfft_amd import _native as N
+    assert (snap.F32, snap.F64, snap.PASS_ROW, snap.VARIANT_INTERLEAVED_ONLY) == (N.F32, N.F64, N.PASS_ROW, N.VARIANT_INTERLEAVED_ONLY)
+    want, got = snap.load(), snap.record(N.lib)
+    assert want["lengths"] == [1 << k for k in range(1, 19)]
+    for group in ("f32", "f64", "complex32"):
+        assert set(got[group]) == set(want[group])
+        for query in sorted(want[group]):
+            assert got[group][query] == want[group][query], (group, query, [L for L, g, w in zip(want["lengths"], got[group][query], want[group][query]) if g != w])
+    # not vacuous: every query answers yes somewhere and no somewhere, and the families differ from one another where they are known to
+    for group in ("f32", "f64"):
+        for query, answers in want[group].items():
+            assert set(answers) == {0, N.E_UNSUPPORTED}, (group, query)
+        assert want[group]["r2r_row"] != want[group]["real_row"] != want[group]["conv_row_real"] != want[group]["conv_row_complex"]
+    assert set(want["complex32"]["half_kernel"]) == {N.HALF_KERNEL_TILE, N.HALF_KERNEL_ROW, N.E_UNSUPPORTED}
+
+
 def test_planner_follows_a_doctored_tuning_table():
     """The planner holds no measured literal of its own: a table with other fractions / rules (what tools/fused_sweep.py --emit
     writes after a sweep on another part) changes the strategies accordingly, and a broken table is refused when it is loaded."""
