@@ -166,9 +166,11 @@ const char *mifft_last_error(void);
                                     * route, no row-first 2-D kernel, no write-through in the run-time-shaped N-D kernel; 3 = 16-column tiles also for strided passes
                                     * whose rows lie >= 2^16 points apart (round 6: those run on 32-column tiles by default) */
 #define MIFFT_DEBUG_NO_ROWFIRST 10 /* split-complex fp32 2-D persistent launches: 1 = two transposing passes on sibling tiles instead of the row-first kernel (A/B) */
+#define MIFFT_DEBUG_PAIR_LANES 12  /* fp32 interleaved 1-D 2^20 = 1024 x 1024 persistent launches: n = paired-lane form n - 1 of the kernel (A/B): 1 = form 0,
+                                    * 8-byte lanes on every stream; 4 = form 3, 16-byte lanes on every stream (the default, 0) */
 /* keys 1, 4 and 11 are retired (they selected kernel forms that were measured and not adopted): mifft_debug_set and
  * mifft_debug_set_default refuse them with MIFFT_E_INVALID */
-#define MIFFT_DEBUG_KEYS 12
+#define MIFFT_DEBUG_KEYS 13
 /* mifft_debug_set changes a switch for the CALLING THREAD only (a thread that never set a key sees the process default), so a
  * measurement that flips a switch in one thread cannot change the kernels another thread's plan gets; mifft_debug_set_default sets
  * the process default (what the environment variables of pyfft_amd/_debug.py do once, when the library is loaded).  A switch must
@@ -177,6 +179,8 @@ const char *mifft_last_error(void);
 int mifft_debug_set(int32_t key, int32_t value);
 int mifft_debug_set_default(int32_t key, int32_t value);
 int mifft_debug_get(int32_t key);
+/* the paired-lane form (MIFFT_DEBUG_PAIR_LANES) the calling thread's last fp32 1-D 1024 x 1024 persistent launch took, -1 before the first */
+int mifft_debug_last_pair_lanes_form(void);
 
 /* ---- runtime shim (replaces cuda.py Context: allocate / stream lifecycle / device limits) ---------- */
 int mifft_device_count(int *count);

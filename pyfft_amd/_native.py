@@ -46,7 +46,8 @@ DEBUG_NO_ND2, DEBUG_NO_WAVE, DEBUG_FORCE_WAVE, DEBUG_ALT_ROWS, DEBUG_PAIR, DEBUG
 DEBUG_ROWS_ND = 8
 DEBUG_NARROW_TILES = 9
 DEBUG_NO_ROWFIRST = 10
-DEBUG_KEYS = 12     # MIFFT_DEBUG_KEYS; keys 1, 4 and 11 are retired (mifft_debug_set refuses them)
+DEBUG_PAIR_LANES = 12
+DEBUG_KEYS = 13     # MIFFT_DEBUG_KEYS; keys 1, 4 and 11 are retired (mifft_debug_set refuses them)
 
 
 class MifftPass(ctypes.Structure):
@@ -183,6 +184,7 @@ PROTOTYPES = {
     "mifft_debug_set": (ctypes.c_int, [_i32, _i32]),
     "mifft_debug_set_default": (ctypes.c_int, [_i32, _i32]),
     "mifft_debug_get": (ctypes.c_int, [_i32]),
+    "mifft_debug_last_pair_lanes_form": (ctypes.c_int, []),
     "mifft_device_count": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)]),
     "mifft_set_device": (ctypes.c_int, [ctypes.c_int]),
     "mifft_get_device": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)]),

@@ -92,12 +92,34 @@ struct TileNoHook {
     __device__ __forceinline__ void operator()() const {}
 };
 
+// The half-wave exchange of PAIR_IN / PAIR_OUT: lanes 32-63 of `lo` trade places with lanes 0-31 of `hi` (v_permlane32_swap_b32
+// vdst = lo, src = hi, one per dword; the builtin, so that the hazard recogniser places the wait states behind a VALU write of an
+// operand).  Before: the lower half-wave holds (p, q) and the upper (r, s); after: the lower holds (p, r), the upper (q, s).
+__device__ __forceinline__ void pair_swap(cplx<float>& lo, cplx<float>& hi) {
+    // (the components are copied into scalars first: __builtin_bit_cast applied to a vector-element lvalue lo.x compiled to one
+    // swap whose first result filled all four dwords)
+    const float lx = lo.x, ly = lo.y, hx = hi.x, hy = hi.y;
+    const auto rx = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, lx), __builtin_bit_cast(unsigned, hx), false, false);
+    const auto ry = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, ly), __builtin_bit_cast(unsigned, hy), false, false);
+    const unsigned ax = rx[0], bx = rx[1], ay = ry[0], by = ry[1];
+    lo.x = __builtin_bit_cast(float, ax); hi.x = __builtin_bit_cast(float, bx);
+    lo.y = __builtin_bit_cast(float, ay); hi.y = __builtin_bit_cast(float, by);
+}
+
 // WIDE (second batch of round 4; 512-thread work-groups): TWO adjacent 16-column tiles interleaved at LANE level -- thread index p
 //     = (b0, c32) with c32 < 32 the column within the 32-column double tile at rem0 (a multiple of 32), so that one wave instruction
 //     touches 32 adjacent columns: whole 128-byte lines of an fp32 plane.  Each half (sub = c32 >> 4) runs the ordinary tile on its
 //     own LDS slab (lds + sub * ELEMS); the arithmetic and the exchange layout per half are unchanged.
+//
+// PAIR_IN / PAIR_OUT (fp32 interleaved on that side, 16-column tile): 16 bytes per lane on the load / store side WITHOUT a second
+//     column per thread.  Lanes i and i + 32 of a wave own two adjacent columns (adjacent q on a transposing store); each of them
+//     fetches 16 bytes -- both columns -- of a DIFFERENT row and the two trade halves (pair_swap), after which every lane holds
+//     its own column of both rows: the points, the registers and the arithmetic per point are those of the plain tile, only which
+//     lane computes which (b0, c) / (u, c2) differs, so the results are bit-identical.  Half the vector-memory instructions, the
+//     same addresses and bytes.  The bases of a paired side must be 16-byte aligned (the launcher's to check).
 template <typename T, int A, bool TR, bool TW, bool SPLIT, bool WT = false, bool NTIN = false, bool NTOUT = false,
-          bool SPLIT_OUT = SPLIT, bool WIDE = false, typename LdsPtr = cplx<T>*, typename Hook = TileNoHook>
+          bool SPLIT_OUT = SPLIT, bool WIDE = false, bool PAIR_IN = false, bool PAIR_OUT = false, typename LdsPtr = cplx<T>*,
+          typename Hook = TileNoHook>
 __device__ __forceinline__ void col2_tile(const TileArgs& a, const long long o_in, const long long o_out,
                                           const long long rem0, LdsPtr lds, Hook hook = Hook(), const int tid_in = -1) {
     constexpr int L = A * 256;
@@ -106,12 +128,19 @@ __device__ __forceinline__ void col2_tile(const TileArgs& a, const long long o_i
     constexpr int BUF = Col2Lds<A, TR, sizeof(cplx<T>)>::BUF;
     constexpr bool kDoubleBuf = Col2Lds<A, TR, sizeof(cplx<T>)>::DOUBLE;
     constexpr bool kHalf = Col2Lds<A, TR, sizeof(cplx<T>)>::HALF;
+    static_assert(!(PAIR_IN || PAIR_OUT) || (sizeof(T) == 4 && !WIDE && !kHalf), "paired lanes: fp32 16-column tiles only");
+    static_assert(!PAIR_IN || !SPLIT, "PAIR_IN: interleaved input only");
+    static_assert(!PAIR_OUT || !SPLIT_OUT, "PAIR_OUT: interleaved output only");
+    typedef T vec4 __attribute__((ext_vector_type(4)));   // the 16 bytes of a paired access
 
     // tid_in: the thread's index within the tile when a bigger work-group runs several tiles side by side (fft_fused2s_kernel)
     int tid = tid_in >= 0 ? tid_in : (int)threadIdx.x;
     asm volatile("" : "+v"(tid));  // same reason as below, for the per-thread (VGPR) address pieces
     // WIDE: cg = the thread's column within the double tile (global addressing), c = within its half (LDS indices)
-    const int cg = WIDE ? (tid & 31) : (tid & 15), b0 = WIDE ? (tid >> 5) : (tid >> 4);
+    // paired lanes: lane and lane + 32 own adjacent indices pair_i = 2i, 2i + 1 of the same pair_j (four pair_j per wave)
+    const int upper = (tid >> 5) & 1;
+    const int pair_i = ((tid & 7) << 1) | upper, pair_j = ((tid >> 6) << 2) | ((tid >> 3) & 3);
+    const int cg = PAIR_IN ? pair_i : WIDE ? (tid & 31) : (tid & 15), b0 = PAIR_IN ? pair_j : WIDE ? (tid >> 5) : (tid >> 4);
     const int c = cg & 15;
     if constexpr (WIDE) lds = lds + (cg >> 4) * Col2Lds<A, TR, sizeof(cplx<T>)>::ELEMS;
     // The shift amounts are laundered through an empty asm so that, when this body sits inside the persistent
@@ -129,7 +158,22 @@ __device__ __forceinline__ void col2_tile(const TileArgs& a, const long long o_i
     {
         const long long ubase = o_in * a.ostride_in + rem0;  // uniform, elements
         const unsigned voff = (((unsigned)b0 << logMS) + (unsigned)cg);
-        if constexpr (!SPLIT) {
+        if constexpr (PAIR_IN) {
+            // rows k = 2m and 2m + 1 differ in b1 only: the upper half-wave reads the row 16A << logMS elements further on, both
+            // halves the column pair (cg & ~1, cg | 1)
+            const char* src = reinterpret_cast<const char*>(reinterpret_cast<const cplx<T>*>(a.in0) + ubase);
+            const unsigned vb = ((((unsigned)b0 + (upper ? 16u * A : 0u)) << logMS) + (unsigned)(cg & ~1)) * (unsigned)sizeof(cplx<T>);
+            static_for<PPT / 2>([&](auto mm) {
+                constexpr int k = 2 * mm, ia = k >> 4, b1 = k & 15;
+                const char* p = src + (((long long)(b1 * 16 * A + ia * 16) << logMS) * (long long)sizeof(cplx<T>));
+                vec4 w;
+                if constexpr (NTIN)
+                    w = __builtin_nontemporal_load(reinterpret_cast<const vec4*>(p + vb));
+                else
+                    w = *reinterpret_cast<const vec4*>(p + vb);
+                v[k].x = w.x; v[k].y = w.y; v[k + 1].x = w.z; v[k + 1].y = w.w;   // (traded below, behind the look-ups)
+            });
+        } else if constexpr (!SPLIT) {
             const char* src = reinterpret_cast<const char*>(reinterpret_cast<const cplx<T>*>(a.in0) + ubase);
             const unsigned vb = voff * (unsigned)sizeof(cplx<T>);
             static_for<PPT>([&](auto kk) {
@@ -172,6 +216,10 @@ __device__ __forceinline__ void col2_tile(const TileArgs& a, const long long o_i
         });
     }
     __builtin_amdgcn_sched_barrier(0);
+    if constexpr (PAIR_IN) {
+        // (row 2m: columns 2i, 2i + 1 | row 2m + 1: the same) -> every lane its own column of rows 2m and 2m + 1 = v[2m], v[2m + 1]
+        static_for<PPT / 2>([&](auto mm) { pair_swap(v[2 * mm], v[2 * mm + 1]); });
+    }
     static_for<PPT>([&](auto kk) {
         constexpr int k = kk;
         v[k].y *= csign;
@@ -233,16 +281,20 @@ __device__ __forceinline__ void col2_tile(const TileArgs& a, const long long o_i
     // phase-2 thread roles: non-TR (u = tid>>4, c2 = tid&15): lanes along the columns (128-byte row segments)
     //                       TR     (u = tid&15, c2 = tid>>4): lanes along q (the write is contiguous in q)
     // (WIDE: the same roles within the thread's half; c2g = its column within the double tile)
-    const int u = TR ? c : b0;
-    const int c2 = TR ? b0 : c;
+    // PAIR_OUT: the paired lanes are adjacent in the contiguous direction of the pass's store -- q (u) when TR, else the column (c2)
+    const int u = PAIR_OUT ? (TR ? pair_i : pair_j) : TR ? c : b0;
+    const int c2 = PAIR_OUT ? (TR ? pair_j : pair_i) : TR ? b0 : c;
     const int c2g = WIDE ? ((cg & 16) + c2) : c2;
+    // where the thread's store starts: its own point, or (PAIR_OUT) the even one of the pair
+    const int c2s = (PAIR_OUT && !TR) ? (c2g & ~1) : c2g;
+    const int us = (PAIR_OUT && TR) ? (u & ~1) : u;
     // output addressing, again uniform base + 32-bit per-thread offset.  The tile's 16 columns start at rem0
     // (a multiple of 16): l0/jp0 are uniform, (dl, djp) is the per-thread part (dl > 0 only when S < 16).
     const long long l0 = rem0 >> logS;
     const long long jp0 = rem0 & ((1ll << logS) - 1);
-    const unsigned dl = (unsigned)(((rem0 + c2g) >> logS) - l0);
-    const unsigned djp = (unsigned)(((rem0 + c2g) & ((1ll << logS) - 1)) - jp0);
-    const unsigned l = (unsigned)l0 + dl;  // row index of this thread's column in the inter-pass twiddle
+    const unsigned dl = (unsigned)(((rem0 + c2s) >> logS) - l0);
+    const unsigned djp = (unsigned)(((rem0 + c2s) & ((1ll << logS) - 1)) - jp0);
+    const unsigned l = PAIR_OUT ? (unsigned)((rem0 + c2g) >> logS) : (unsigned)l0 + dl;  // row index of this thread's column in the inter-pass twiddle
     const T sx = (T)a.scale;
     const T sy = a.inverse ? -sx : sx;
     cplx<T> sxy;
@@ -256,7 +308,9 @@ __device__ __forceinline__ void col2_tile(const TileArgs& a, const long long o_i
     // non-TR: out[o][l][q][jp] -> uniform o*ostride + ((l0*L + qconst) << logS) + jp0 ; thread ((dl*L + u) << logS) + djp
     // TR (S == 1): out[o][l][q] -> uniform o*ostride + rem0*L + qconst ; thread c2*L + u
     const long long oubase = TR ? (a.ostride_out * o_out + rem0 * L) : (a.ostride_out * o_out + ((l0 * L) << logS) + jp0);
-    const unsigned ovoff = TR ? ((unsigned)c2g * L + (unsigned)u) : ((((unsigned)dl * L + (unsigned)u) << logS) + djp);
+    // (PAIR_OUT: after the trade the upper half-wave holds output row qb0 + 1, one step of 16A in q further on)
+    const unsigned ovoff = (TR ? ((unsigned)c2g * L + (unsigned)us) : ((((unsigned)dl * L + (unsigned)us) << logS) + djp)) +
+                           ((PAIR_OUT && upper) ? (TR ? 16u * A : ((16u * A) << logS)) : 0u);
 
     // The anchors of the inter-pass twiddle (TW) are looked up ONE ROUND AHEAD, in one batch issued before the previous round's
     // stores: the wait for them then covers stores that are a whole round old.  (Round 6: issued inside their own round they sat
@@ -356,6 +410,25 @@ __device__ __forceinline__ void col2_tile(const TileArgs& a, const long long o_i
                 });
             });
         }
+        if constexpr (PAIR_OUT) {
+            // rows qb0 and qb0 + 1 of the pair's two points -> the lower half-wave 16 contiguous bytes of row qb0, the upper of qb0 + 1
+            static_for<8>([&](auto hh) {
+                constexpr int qb0 = 2 * hh;
+                const long long gu = TR ? (oubase + qb0 * 16 * A + 16 * qa)
+                                        : (oubase + ((long long)(qb0 * 16 * A + 16 * qa) << logS));
+                cplx<T> r0 = x[qb0] * sxy, r1 = x[qb0 + 1] * sxy;
+                pair_swap(r0, r1);
+                vec4 w;
+                w.x = r0.x; w.y = r0.y; w.z = r1.x; w.w = r1.y;
+                char* p = reinterpret_cast<char*>(reinterpret_cast<cplx<T>*>(a.out0) + gu);
+                if constexpr (WT)
+                    store_b128_sc1(p, ovoff * (unsigned)sizeof(cplx<T>), __builtin_bit_cast(unsigned __attribute__((ext_vector_type(4))), w));
+                else if constexpr (NTOUT)
+                    __builtin_nontemporal_store(w, reinterpret_cast<vec4*>(p + ovoff * (unsigned)sizeof(cplx<T>)));
+                else
+                    *reinterpret_cast<vec4*>(p + ovoff * (unsigned)sizeof(cplx<T>)) = w;
+            });
+        } else {
         static_for<16>([&](auto qq) {
             constexpr int qb0 = qq;
             // uniform part of the output element index
@@ -387,6 +460,7 @@ __device__ __forceinline__ void col2_tile(const TileArgs& a, const long long o_i
                 }
             }
         });
+        }
     });
 }
 

@@ -255,8 +255,13 @@ __device__ __forceinline__ void fused_loop(const FusedCtl& f, unsigned* s_item, 
 
 // NT: 0 = plain accesses on the streamed side, 1 = non-temporal loads of the input and stores of the output, 2 = non-temporal
 // loads and write-through (sc1) stores of the output (A/B; non-temporal loads of the RING in pass 1 measured 0.6 % slower on C2)
-template <typename T, int A0, int A1, bool SPLIT, int NT>
+// PAIR0 / PAIR1: the paired-lane streams of pass 0 / pass 1 (kPairIn | kPairOut, col2_tile PAIR_IN / PAIR_OUT: 16 bytes per lane on
+// that side of the pass); fp32 interleaved 1024 x 1024 only.  The ring side keeps the hand-off: sc1 stores (16 bytes: the raw-buffer
+// form of the fp64 ring), plain loads behind the acquire.
+constexpr int kPairIn = 1, kPairOut = 2;
+template <typename T, int A0, int A1, bool SPLIT, int NT, int PAIR0 = 0, int PAIR1 = 0>
 __global__ void __launch_bounds__(256, 2) fft_fused2_kernel(const FusedArgs f) {
+    static_assert((PAIR0 | PAIR1) == 0 || (sizeof(T) == 4 && A0 == 4 && A1 == 4 && !SPLIT && NT == 1), "paired lanes: <float, 4, 4, false, 1> only");
     constexpr int E0 = Col2Lds<A0, true, sizeof(cplx<T>)>::ELEMS, E1 = Col2Lds<A1, false, sizeof(cplx<T>)>::ELEMS;
     __shared__ __attribute__((aligned(16))) cplx<T> lds[E0 > E1 ? E0 : E1];
     __shared__ unsigned s_item;
@@ -265,10 +270,12 @@ __global__ void __launch_bounds__(256, 2) fft_fused2_kernel(const FusedArgs f) {
     fused_loop<per0, per1, !SPLIT && sizeof(T) == 4>(   // early poll: C2 19.49 -> 19.32 ms; split planes 26.7 -> 25.6 ms WITHOUT it; fp64: no register to spare
         f.c, &s_item,
         [&](unsigned t, unsigned slot, unsigned tile, auto hook) {
-            col2_tile<T, A0, true, true, SPLIT, true, NT != 0, false, false>(f.p0, (long long)t, (long long)slot, (long long)tile * 16, lds, hook);
+            col2_tile<T, A0, true, true, SPLIT, true, NT != 0, false, false, false, (PAIR0 & kPairIn) != 0, (PAIR0 & kPairOut) != 0>(
+                f.p0, (long long)t, (long long)slot, (long long)tile * 16, lds, hook);
         },
         [&](unsigned slot, unsigned t, unsigned tile, auto hook) {
-            col2_tile<T, A1, false, false, false, NT == 2, false, NT == 1, SPLIT>(f.p1, (long long)slot, (long long)t, (long long)tile * 16, lds, hook);
+            col2_tile<T, A1, false, false, false, NT == 2, false, NT == 1, SPLIT, false, (PAIR1 & kPairIn) != 0, (PAIR1 & kPairOut) != 0>(
+                f.p1, (long long)slot, (long long)t, (long long)tile * 16, lds, hook);
         });
 }
 
@@ -341,6 +348,7 @@ __global__ void __launch_bounds__(256, 2) fft_fused2m_kernel(const FusedArgs f) 
 // out[ky][kx] -- i.e. the 1-D kernel above minus the twiddle, with contiguous 8 KiB runs on the output side.
 // Round 4: rectangles.  A0 = ny / 256 (pass 0 transforms the y axis over nx / 16 tiles), A1 = nx / 256 (pass 1 the x axis over
 // ny / 16 tiles); the two passes look their w(L) up in different tables (TileArgs.tw_L of p0 / p1).
+// (The paired lanes of fft_fused2_kernel lost here: 2.46 against 2.43 ms on configuration 3, docs/negative_results.md.)
 template <typename T, int A0, int A1, bool SPLIT, bool NT>
 __global__ void __launch_bounds__(256, 2) fft_fused2d_kernel(const FusedArgs f) {
     constexpr int E0 = Col2Lds<A0, true, sizeof(cplx<T>)>::ELEMS, E1 = Col2Lds<A1, true, sizeof(cplx<T>)>::ELEMS;

@@ -8,6 +8,24 @@ namespace {
 // tiles (shorter passes run the 32-column tiles of fft_fused2d_f32.hip), both streamed non-temporally, L0 >= L1 (the chain's
 // factorisation puts the larger radix first).  A development switch that asks for another form (MIFFT_NARROW_TILES=1, MIFFT_STORE)
 // gets -2.
+// The paired-lane forms of the 1024 x 1024 kernel (fft_col2.hpp PAIR_IN / PAIR_OUT; docs/persistent.md): form 0 moves 8 bytes per lane
+// on all four streams of the kernel, form 3 -- the default -- sixteen on all four (forms 1 and 2, the ring side alone, were measured
+// and not kept: docs/negative_results.md).  Form 0 is also what runs when a user buffer is not 16-byte aligned (the ring is the
+// plan's own allocation and always is; mifft_launch_fused2 refuses such buffers today, so this is the kernel's own second line).
+// MIFFT_DEBUG_PAIR_LANES = n asks for form n - 1 (0: the default); a form this library has no instance of gets -2, never another kernel.
+constexpr int kPairLanesDefault = 3;
+int launch_1024(const mifft::FusedArgs* f, unsigned grid, hipStream_t s) {
+    constexpr int kPairAll = mifft::kPairIn | mifft::kPairOut;
+    const int sw = mifft_debug_get(MIFFT_DEBUG_PAIR_LANES);
+    int form = sw == 0 ? kPairLanesDefault : sw - 1;
+    if (form != 0 && form != 3) return -2;
+    if ((((uintptr_t)f->p0.in0 | (uintptr_t)f->p1.out0) & 15) != 0) form = 0;
+    if (form == 3) hipLaunchKernelGGL((mifft::fft_fused2_kernel<float, 4, 4, false, 1, kPairAll, kPairAll>), dim3(grid), dim3(256), 0, s, *f);
+    else hipLaunchKernelGGL((mifft::fft_fused2_kernel<float, 4, 4, false, 1>), dim3(grid), dim3(256), 0, s, *f);
+    mifft_note_pair_lanes_form(form);
+    return (int)hipGetLastError();
+}
+
 template <int A0, int A1> int launch(const mifft::FusedArgs* f, int split, unsigned grid, hipStream_t s) {
     if constexpr (A0 < A1) {
         return -2;
@@ -18,6 +36,8 @@ template <int A0, int A1> int launch(const mifft::FusedArgs* f, int split, unsig
         if (mifft_debug_get(MIFFT_DEBUG_NARROW_TILES) == 1 || store == 2 || store == 3) return -2;
         if (split) {
             hipLaunchKernelGGL((mifft::fft_fused2s_kernel<A0, A1, false, true>), dim3(grid), dim3(512), 0, s, *f);
+        } else if constexpr (A0 == 4 && A1 == 4) {
+            return launch_1024(f, grid, s);
         } else if constexpr (A0 == 4) {
             hipLaunchKernelGGL((mifft::fft_fused2_kernel<float, A0, A1, false, 1>), dim3(grid), dim3(256), 0, s, *f);
         } else {

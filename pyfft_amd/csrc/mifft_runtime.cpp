@@ -24,6 +24,7 @@ thread_local char g_err[512] = "";
 std::atomic<int> g_debug_default[MIFFT_DEBUG_KEYS];
 thread_local int t_debug_value[MIFFT_DEBUG_KEYS];
 thread_local unsigned t_debug_mask = 0;
+thread_local int t_pair_lanes_form = -1;   // form of this thread's last fp32 1-D 1024 x 1024 persistent launch (mifft_debug_last_pair_lanes_form)
 struct DebugSwitches {
     int operator[](int key) const {
         return ((t_debug_mask >> key) & 1u) ? t_debug_value[key] : g_debug_default[key].load(std::memory_order_relaxed);
@@ -553,6 +554,8 @@ int mifft_debug_set_default(int32_t key, int32_t value) {
     return 0;
 }
 int mifft_debug_get(int32_t key) { return (key >= 0 && key < MIFFT_DEBUG_KEYS) ? g_debug[key] : 0; }
+void mifft_note_pair_lanes_form(int form) { t_pair_lanes_form = form; }
+int mifft_debug_last_pair_lanes_form(void) { return t_pair_lanes_form; }
 const char* mifft_last_error(void) { return g_err; }
 
 int mifft_device_count(int* count) {

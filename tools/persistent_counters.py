@@ -5,7 +5,7 @@ Run ON THE GPU BOX from the repo root:
 
     cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT && python3 tools/persistent_counters.py [--out FILE] [case ...]
 
-A case is a name of CASES below (default: all of them).  For every case and every counter group one run of
+A case is a name of CASES below (default: all of them); --groups 0,1,... restricts the run to those entries of GROUPS.  For every case and every counter group one run of
 `rocprofv3 --pmc <group> --kernel-trace -- python3 bench.py <case args> --plain` (counters in their own runs, the program
 directly after `--`; a group that the part rejects is retried one counter at a time and the rejected names are listed).
 The table printed at the end has one column per case, one row per counter: the SUM over the kernel's dispatches divided
@@ -89,6 +89,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("cases", nargs="*", default=[])
     ap.add_argument("--out", default=None)
+    ap.add_argument("--groups", default=None, help="comma-separated indices into GROUPS (default: every group)")
     a = ap.parse_args()
     cases = a.cases or list(CASES)
     os.environ.setdefault("TMPDIR", "/tmp")
@@ -99,6 +100,7 @@ def main():
         out.flush()
 
     names = available()
+    GROUPS[:] = [GROUPS[int(i)] for i in a.groups.split(",")] if a.groups else GROUPS
     groups = GROUPS
     if names:
         groups = [[c for c in g if c in names] for g in GROUPS]
