@@ -7,9 +7,9 @@ extern "C" int mifft_conv_row_dispatch_f32(int real, int L, const mifft::ConvRow
     using namespace mifft;
     int rc = -2;
     // real rows of 32768 and 65536 reals: the pair epilogue spills beyond the real row kernels of the same length (500 / 540 bytes
-    // of scratch against 376 / 348), so those lengths run the composed form (docs/extensions.md "Convolution plans")
+    // of scratch against 376 / 348), so those lengths run the composed form (docs/extensions.md "Convolution plans") and build no real kernel
     for_length<2, 4, 8, 16, 32>(L, rc, [&](auto l) { return launch_conv_row_small<float, l>(real, a, s, query_only); }) ||
         for_length<64, 128, 256, 512, 1024, 2048, 4096, 8192>(L, rc, [&](auto l) { return launch_conv_row<float, l>(real, a, s, query_only); }) ||
-        for_length<16384, 32768>(L, rc, [&](auto l) { return real ? -2 : launch_conv_row<float, l>(real, a, s, query_only); });
+        for_length<16384, 32768>(L, rc, [&](auto l) { return launch_conv_row<float, l, false>(real, a, s, query_only); });
     return rc;
 }

@@ -7,9 +7,10 @@ extern "C" int mifft_conv_row_dispatch_f64(int real, int L, const mifft::ConvRow
     using namespace mifft;
     int rc = -2;
     // real rows of 16384 and 32768 reals spill (308 / 836 bytes of scratch against 0 / 168 for the real rows), and so does the
-    // complex row of 16384 points (272 against 0): those run the composed form (docs/extensions.md "Convolution plans")
+    // complex row of 16384 points (272 against 0): those run the composed form (docs/extensions.md "Convolution plans"); L = 8192
+    // builds the complex kernel only
     for_length<2, 4, 8, 16, 32>(L, rc, [&](auto l) { return launch_conv_row_small<double, l>(real, a, s, query_only); }) ||
         for_length<64, 128, 256, 512, 1024, 2048, 4096>(L, rc, [&](auto l) { return launch_conv_row<double, l>(real, a, s, query_only); }) ||
-        for_length<8192>(L, rc, [&](auto l) { return real ? -2 : launch_conv_row<double, l>(real, a, s, query_only); });
+        for_length<8192>(L, rc, [&](auto l) { return launch_conv_row<double, l, false>(real, a, s, query_only); });
     return rc;
 }

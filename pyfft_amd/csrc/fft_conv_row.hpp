@@ -8,9 +8,9 @@
 //            the scale (1/n folded in by the host), so one twiddle table serves both directions.
 //            The inverse takes the REVERSED radix list: its first radix is the forward's last, so the forward's last-stage register
 //            layout is the inverse's first-stage load layout for every list, and no LDS exchange joins the two transforms.
-//   real     n real points as L = n / 2 packed complex points (csrc/fft_real.hip states the identities).  The forward packed stages run;
-//            one mirror exchange through the row's LDS slab (as RealSepEpi) gives the thread that holds Z[k] also Z[L - k]; from that
-//            pair it derives X[k] and X[L - k], multiplies them by S[k] and S[L - k] and packs Z'[k] from the two products -- exactly
+//   real     n real points as L = n / 2 packed complex points (csrc/fft_real.hip derives the identities, fft_real_ident.hpp holds them).
+//            The forward packed stages run; one mirror exchange through the row's LDS slab (real_mirror_pairs, as RealSepEpi) gives the
+//            thread that holds Z[k] also Z[L - k]; from that pair it derives X[k] and X[L - k], multiplies them by S[k] and S[L - k] and packs Z'[k] from the two products -- exactly
 //            the pair the packing identity needs, so no second exchange.  Index 0 takes X[0] and X[L] through their real parts (the
 //            edge rule of real_row_inv_kernel, numpy's irfft).  The inverse L-point stages store the n reals.
 // Rows of L <= 32 (complex or packed points): one thread per row, both transforms in registers (Dft<L>), as real_row_small_kernel.
@@ -80,86 +80,33 @@ template <typename T, int L, int W, bool HALF, typename RL> struct ConvEpi {
     }
 };
 
-// Z'[k] from s = Z[k] + conj Z[L - k], d = Z[k] - conj Z[L - k] (Z the packed forward transform):
-//   X[k] = 1/2 (s - i t), X[L - k] = conj(1/2 (s + i t)), t = w(n)^k d;   Y = X * S;   at k = 0 the pair is X[0], X[L], real parts only
-//   Z'[k] = (Y[k] + conj Y[L - k]) + i conj(w(n)^k) (Y[k] - conj Y[L - k])
-// and the unnormalised inverse transform of Z' is n times the inverse real transform of Y, packed.
+// Z'[k] from the s, d of the packed forward transform Z at idx = k: the separated pair X[k], X[L - k];  Y = X * S;  at k = 0 the pair is
+// X[0], X[L], real parts only;  Z'[k] packed from the s, d of the pair Y[k], Y[L - k].  The unnormalised inverse transform of Z' is n
+// times the inverse real transform of Y, packed.
 template <typename T, int L>
 __device__ __forceinline__ cplx<T> conv_real_pair(cplx<T> s, cplx<T> d, int idx, const TileArgs& a, bool valid) {
     const cplx<T> w = reinterpret_cast<const cplx<T>*>(a.tw_lo)[idx];
-    const cplx<T> t = {w.x * d.x - w.y * d.y, w.x * d.y + w.y * d.x};
     const T h = (T)0.5;
-    cplx<T> y1 = cmul<T>(cplx<T>{(s.x + t.y) * h, (s.y - t.x) * h}, conv_spec<T>(a, idx, valid));
-    cplx<T> y2 = cmul<T>(cplx<T>{(s.x - t.y) * h, -(s.y + t.x) * h}, conv_spec<T>(a, L - idx, valid));
+    cplx<T> y1 = cmul<T>(real_sep<T>(s, w, d, h), conv_spec<T>(a, idx, valid));
+    cplx<T> y2 = cmul<T>(real_sep_mirror<T>(s, w, d, h), conv_spec<T>(a, L - idx, valid));
     if (idx == 0) {
         y1.y = 0;
         y2.y = 0;
     }
-    const cplx<T> sm = {y1.x + y2.x, y1.y - y2.y}, df = {y1.x - y2.x, y1.y + y2.y};
-    const cplx<T> u = {w.x * df.x + w.y * df.y, w.x * df.y - w.y * df.x};     // conj(w) df
-    return cplx<T>{sm.x - u.y, sm.y + u.x};
+    cplx<T> sm, df;
+    real_sd<T>(y1, y2, sm, df);
+    return real_pack<T>(sm, w, df);
 }
 
 template <typename T, int L, int W, bool HALF, typename RL> struct ConvRealEpi {
     template <int NB, int R, int TPR, int LR, typename LdsT>
     static __device__ __forceinline__ void run(LdsT* lds, cplx<T>* v, const TileArgs& a, int tid, char* outb, bool valid) {
         static_assert(FirstRadix<typename ReverseRadices<RL>::type>::value == R, "the inverse starts with the forward's last radix");
-        __syncthreads();       // every thread has fetched its last-stage operands: the slab is free
-        if constexpr (!HALF) {
-            static_for<NB>([&](auto bb) {
-                static_for<R>([&](auto kk) {
-                    constexpr int b = bb, k = kk;
-                    lds[row2_pad(b * TPR + k * LR + tid)] = v[b * R + k];
-                });
-            });
-            __syncthreads();
-            static_for<NB>([&](auto bb) {
-                static_for<R>([&](auto kk) {
-                    constexpr int b = bb, k = kk;
-                    const int idx = b * TPR + k * LR + tid;
-                    const cplx<T> p = v[b * R + k], q = lds[row2_pad((L - idx) & (L - 1))];
-                    v[b * R + k] = conv_real_pair<T, L>(cplx<T>{p.x + q.x, p.y - q.y}, cplx<T>{p.x - q.x, p.y + q.y}, idx, a, valid);
-                    conv_group_fence();
-                });
-            });
-        } else {
-            // the slab holds L scalars: real parts, then imaginary parts (RealSepEpi).  After the first round v[i].x holds s.x, dx[i] d.x.
-            T dx[NB * R];
-            static_for<NB>([&](auto bb) {
-                static_for<R>([&](auto kk) {
-                    constexpr int b = bb, k = kk;
-                    lds[row2_pad(b * TPR + k * LR + tid)] = v[b * R + k].x;
-                });
-            });
-            __syncthreads();
-            static_for<NB>([&](auto bb) {
-                static_for<R>([&](auto kk) {
-                    constexpr int b = bb, k = kk;
-                    const int idx = b * TPR + k * LR + tid;
-                    const T qx = lds[row2_pad((L - idx) & (L - 1))];
-                    dx[b * R + k] = v[b * R + k].x - qx;
-                    v[b * R + k].x += qx;
-                });
-            });
-            __syncthreads();
-            static_for<NB>([&](auto bb) {
-                static_for<R>([&](auto kk) {
-                    constexpr int b = bb, k = kk;
-                    lds[row2_pad(b * TPR + k * LR + tid)] = v[b * R + k].y;
-                });
-            });
-            __syncthreads();
-            static_for<NB>([&](auto bb) {
-                static_for<R>([&](auto kk) {
-                    constexpr int b = bb, k = kk;
-                    const int idx = b * TPR + k * LR + tid;
-                    const T qy = lds[row2_pad((L - idx) & (L - 1))];
-                    const T py = v[b * R + k].y;
-                    v[b * R + k] = conv_real_pair<T, L>(cplx<T>{v[b * R + k].x, py - qy}, cplx<T>{dx[b * R + k], py + qy}, idx, a, valid);
-                    conv_group_fence();
-                });
-            });
-        }
+        // every row is live: one outside the launch carries zeros (conv_spec) into the inverse stages
+        real_mirror_pairs<T, L, HALF, NB, R, TPR, LR>(lds, v, tid, IC<1>{}, [&](auto i, int idx, cplx<T> s, cplx<T> d) __attribute__((always_inline)) {
+            v[i] = conv_real_pair<T, L>(s, d, idx, a, valid);
+            conv_group_fence();
+        });
         conv_inverse<T, L, W, HALF, RL, TPR>(lds, v, a, tid, outb, valid);
     }
 };
@@ -200,8 +147,9 @@ __device__ __forceinline__ void conv_row_body(const ConvRowArgs& a) {
             cplx<T> z[L];
             static_for<L>([&](auto kk) {
                 constexpr int k = kk;
-                const cplx<T> p = v[k], q = v[(L - k) & (L - 1)];
-                const cplx<T> y = conv_real_pair<T, L>(cplx<T>{p.x + q.x, p.y - q.y}, cplx<T>{p.x - q.x, p.y + q.y}, k, t, true);
+                cplx<T> s, d;
+                real_sd<T>(v[k], v[(L - k) & (L - 1)], s, d);
+                const cplx<T> y = conv_real_pair<T, L>(s, d, k, t, true);
                 z[k] = cplx<T>{y.x, -y.y};
             });
             static_for<L>([&](auto k) { v[k] = z[k]; });
@@ -214,6 +162,7 @@ __device__ __forceinline__ void conv_row_body(const ConvRowArgs& a) {
         constexpr int PPT = G::PPT, LP = G::LP;
         using LdsT = typename std::conditional<HALF, T, cplx<T>>::type;
         __shared__ __attribute__((aligned(16))) LdsT lds[W * LP];
+        // (the row preamble written out, not Row2Geom::lane: through the function the W > 1 kernels schedule differently)
         const int c = W == 1 ? 0 : threadIdx.x / TPR, u = W == 1 ? threadIdx.x : threadIdx.x % TPR;
         const long long row = (long long)blockIdx.x * W + c;
         const bool valid = row < a.rows;
@@ -221,11 +170,7 @@ __device__ __forceinline__ void conv_row_body(const ConvRowArgs& a) {
         const char* inb = reinterpret_cast<const char*>(reinterpret_cast<const cplx<T>*>(a.in) + row * L);
         char* outb = reinterpret_cast<char*>(reinterpret_cast<cplx<T>*>(a.out) + row * L);
         unsigned voff = (unsigned)u * (unsigned)sizeof(cplx<T>);
-        if constexpr (W > 1) {  // the row differs across the wave: fold the thread's offset into its own 64-bit base
-            inb += voff;
-            outb += voff;
-            voff = 0;
-        }
+        row2_fold_offset<W>(voff, inb, outb);
         using Epi = typename std::conditional<REAL, ConvRealEpi<T, L, W, HALF, RL>, ConvEpi<T, L, W, HALF, RL>>::type;
         cplx<T> v[PPT];
         Row2Stages<T, L, TPR, 1, true, HALF, RL, 0, Epi>::run(lds + c * LP, v, t, u, inb, outb, voff, valid);
@@ -243,18 +188,23 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(OCC))) 
 }
 
 // real != 0: L packed points (n = 2L reals); 0 launched (query: a kernel exists), -2 none, -1 grid too large
-template <typename T, int L, typename S = Row2Shape<T, L>>
+// REAL_ROWS false: this length has complex rows only, and no real kernel is built for it
+template <typename T, int L, bool REAL_ROWS = true, typename S = Row2Shape<T, L>>
 static inline int launch_conv_row(int real, const ConvRowArgs* a, hipStream_t s, int query_only) {
+    if (real && !REAL_ROWS) return -2;
     return launch_groups(a, &ConvRowArgs::rows, S::W, query_only, [&](dim3 grid) {
-        if (real) hipLaunchKernelGGL((conv_row_real_kernel<T, L, S::W, S::NT, S::HALF, S::OCC, typename S::RL>), grid, dim3(S::NT), 0, s, *a);
-        else hipLaunchKernelGGL((conv_row_kernel<T, L, S::W, S::NT, S::HALF, S::OCC, typename S::RL>), grid, dim3(S::NT), 0, s, *a);
+        auto kernel = conv_row_kernel<T, L, S::W, S::NT, S::HALF, S::OCC, typename S::RL>;
+        if constexpr (REAL_ROWS) {
+            if (real) kernel = conv_row_real_kernel<T, L, S::W, S::NT, S::HALF, S::OCC, typename S::RL>;
+        }
+        hipLaunchKernelGGL(kernel, grid, dim3(S::NT), 0, s, *a);
     });
 }
 
 // L <= 32: one thread per row
 template <typename T, int L>
 static inline int launch_conv_row_small(int real, const ConvRowArgs* a, hipStream_t s, int query_only) {
-    return launch_conv_row<T, L, Row2ShapeOf<256, 256, RadixList<L>>>(real, a, s, query_only);
+    return launch_conv_row<T, L, true, Row2ShapeOf<256, 256, RadixList<L>>>(real, a, s, query_only);
 }
 
 }  // namespace mifft

@@ -3,7 +3,7 @@
 //   forward  load prologue: one 16-byte read of x[4j .. 4j + 3] is z[j] = (x[4j], x[4j + 2]) and z[L - 1 - j] = (x[4j + 3], x[4j + 1])
 //            of the packed permuted row (DST: the odd samples negated); both go to the row's LDS slab, and every thread fetches its
 //            first-stage points from there.  The stages of the complex row of L = n / 2 points run.  The epilogue exchanges the
-//            transform through the slab once more (Z[k] needs Z[L - k], as RealSepEpi), forms 2 V[k] and stores
+//            transform through the slab once more (Z[k] needs Z[L - k]: real_mirror_pairs, as RealSepEpi), forms 2 V[k] and stores
 //            y[k] = Re(t[k] 2V[k]) and y[n - k] = -Im(t[k] 2V[k]) (DST: at n - 1 - k and k - 1): one ascending and one descending run.
 //   inverse  every thread loads the orbit {Y[k], Y[n - k], Y[L + k], Y[L - k]} of its first-stage points (ascending and descending
 //            runs), forms V[k] = u[k] (Y[k] - i Y[n - k]) and V[L + k], and packs Z'[k] = (V[k] + V[L + k]) + i w(n)^-k (V[k] - V[L + k]);
@@ -39,11 +39,11 @@ template <typename T> __device__ __forceinline__ void r2r_store4(T* p, T a, T b,
 
 template <typename T> __device__ __forceinline__ cplx<T> r2r_cmul(cplx<T> a, cplx<T> b) { return {a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
 
-// forward outputs of the point pair (Z[k], Z[L - k]) held as p, q: y[k], y[n - k] (k > 0), and y[L] from k = 0
+// forward outputs of the point pair (Z[k], Z[L - k]) given as its s, d (real_sd): y[k], y[n - k] (k > 0), and y[L] from k = 0.  2V[k]
+// and 2V[L] are real_sep and real_sep_edge with h = 1, written out with r2r_cmul: through those functions the kernels schedule differently
 template <typename T, int L>
-__device__ __forceinline__ void r2r_fwd_emit(T* out, const cplx<T>* sep, const cplx<T>* tab, int dst, int k, cplx<T> p, cplx<T> q) {
+__device__ __forceinline__ void r2r_fwd_emit(T* out, const cplx<T>* sep, const cplx<T>* tab, int dst, int k, cplx<T> s, cplx<T> d) {
     constexpr int n = 2 * L;
-    const cplx<T> s = {p.x + q.x, p.y - q.y}, d = {p.x - q.x, p.y + q.y};
     const cplx<T> t = r2r_cmul(sep[k], d);
     const cplx<T> u = r2r_cmul(tab[k], cplx<T>{s.x + t.y, s.y - t.x});     // t[k] 2V[k]
     out[dst ? n - 1 - k : k] = u.x;
@@ -70,21 +70,8 @@ template <typename T, int L> struct R2rFwdEpi {
         const cplx<T>* sep = reinterpret_cast<const cplx<T>*>(a.tw_lo);
         const cplx<T>* tab = reinterpret_cast<const cplx<T>*>(a.tw_hi);
         T* out = reinterpret_cast<T*>(outb);
-        __syncthreads();       // every thread has fetched its last-stage operands: the slab is free
-        static_for<NB>([&](auto bb) {
-            static_for<R>([&](auto kk) {
-                constexpr int b = bb, k = kk;
-                lds[row2_pad(b * TPR + k * LR + tid)] = v[b * R + k];
-            });
-        });
-        __syncthreads();
-        static_for<NB>([&](auto bb) {
-            static_for<R>([&](auto kk) {
-                constexpr int b = bb, k = kk;
-                const int idx = b * TPR + k * LR + tid;
-                const cplx<T> q = lds[row2_pad((L - idx) & (L - 1))];
-                if (valid) r2r_fwd_emit<T, L>(out, sep, tab, a.has_tw, idx, v[b * R + k], q);
-            });
+        real_mirror_pairs<T, L, false, NB, R, TPR, LR>(lds, v, tid, valid, [&](auto, int idx, cplx<T> s, cplx<T> d) __attribute__((always_inline)) {
+            r2r_fwd_emit<T, L>(out, sep, tab, a.has_tw, idx, s, d);
         });
     }
 };
@@ -121,11 +108,11 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(OCC))) 
     constexpr int LR0 = L / R0;
     static_assert(PPT % 2 == 0, "the load prologue / store epilogue moves four reals per step");
     __shared__ __attribute__((aligned(16))) cplx<T> lds[W * LP];
-    const int c = W == 1 ? 0 : threadIdx.x / TPR, u = W == 1 ? threadIdx.x : threadIdx.x % TPR;
-    const long long row = (long long)blockIdx.x * W + c;
-    const bool valid = row < a.total;
-    const T* x = reinterpret_cast<const T*>(a.in0) + row * (2 * L);
-    cplx<T>* slab = lds + c * LP;
+    const Row2Lane g = G::lane(a.total);
+    const int u = g.u;
+    const bool valid = g.valid;
+    const T* x = reinterpret_cast<const T*>(a.in0) + g.row * (2 * L);
+    cplx<T>* slab = lds + g.c * LP;
     const T so = a.has_tw ? (T)-1 : (T)1;
     static_for<PPT / 2>([&](auto tt) {
         constexpr int t = tt;
@@ -142,7 +129,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(OCC))) 
         v[i] = slab[row2_pad(b * TPR + k * LR0 + u)];
     });
     __syncthreads();       // the first stage's exchange writes the slab
-    char* outb = reinterpret_cast<char*>(reinterpret_cast<T*>(a.out0) + row * (2 * L));
+    char* outb = reinterpret_cast<char*>(reinterpret_cast<T*>(a.out0) + g.row * (2 * L));
     Row2Stages<T, L, TPR, 1, true, false, RL, 0, R2rFwdEpi<T, L>>::template run<true>(slab, v, a, u, nullptr, outb, 0, valid);
 }
 
@@ -154,25 +141,27 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(OCC))) 
     constexpr int LR0 = L / R0;
     static_assert(PPT % 2 == 0, "the load prologue / store epilogue moves four reals per step");
     __shared__ __attribute__((aligned(16))) cplx<T> lds[W * LP];
-    const int c = W == 1 ? 0 : threadIdx.x / TPR, u = W == 1 ? threadIdx.x : threadIdx.x % TPR;
-    const long long row = (long long)blockIdx.x * W + c;
-    const bool valid = row < a.total;
-    const T* y = reinterpret_cast<const T*>(a.in0) + row * (2 * L);
+    const Row2Lane g = G::lane(a.total);
+    const int u = g.u;
+    const T* y = reinterpret_cast<const T*>(a.in0) + g.row * (2 * L);
     const cplx<T>* sep = reinterpret_cast<const cplx<T>*>(a.tw_lo);
     const cplx<T>* tab = reinterpret_cast<const cplx<T>*>(a.tw_hi);
     cplx<T> v[PPT];
     static_for<PPT>([&](auto i) { v[i] = cplx<T>{(T)0, (T)0}; });
-    if (valid) {
+    if (g.valid) {
         static_for<PPT>([&](auto ii) {
             constexpr int i = ii, b = i / R0, k = i % R0;
             v[i] = r2r_inv_pack<T, L>(y, sep, tab, a.has_tw, b * TPR + k * LR0 + u);
         });
     }
-    char* outb = reinterpret_cast<char*>(reinterpret_cast<T*>(a.out0) + row * (2 * L));
-    Row2Stages<T, L, TPR, 1, true, false, RL, 0, R2rInvEpi<T, L>>::template run<true>(lds + c * LP, v, a, u, nullptr, outb, 0, valid);
+    char* outb = reinterpret_cast<char*>(reinterpret_cast<T*>(a.out0) + g.row * (2 * L));
+    Row2Stages<T, L, TPR, 1, true, false, RL, 0, R2rInvEpi<T, L>>::template run<true>(lds + g.c * LP, v, a, u, nullptr, outb, 0, g.valid);
 }
 
 // ---- L <= 32: one thread per row -------------------------------------------------------------------------------------------------
+// the x sample held at real position p (2j = Re, 2j + 1 = Im of z[j]) of the packed permuted row; an odd sample carries the DST's sign
+constexpr int r2r_perm(int L, int p) { return p < L ? 2 * p : 2 * (2 * L - 1 - p) + 1; }
+
 template <typename T, int L, bool INV>
 __global__ void __launch_bounds__(256) r2r_row_small_kernel(const TileArgs a) {
     const long long row = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -187,16 +176,15 @@ __global__ void __launch_bounds__(256) r2r_row_small_kernel(const TileArgs a) {
         T xr[2 * L];
         static_for<2 * L>([&](auto i) { xr[i] = in[i]; });
         static_for<L>([&](auto jj) {
-            constexpr int j = jj;
-            constexpr int p0 = 2 * j, p1 = 2 * j + 1;                     // positions in v
-            constexpr int s0 = p0 < L ? 2 * p0 : 2 * (2 * L - 1 - p0) + 1;  // the x sample at each
-            constexpr int s1 = p1 < L ? 2 * p1 : 2 * (2 * L - 1 - p1) + 1;
+            constexpr int j = jj, s0 = r2r_perm(L, 2 * j), s1 = r2r_perm(L, 2 * j + 1);
             v[j] = cplx<T>{(s0 & 1) ? so * xr[s0] : xr[s0], (s1 & 1) ? so * xr[s1] : xr[s1]};
         });
         Dft<L, T>::run(v);
         static_for<L>([&](auto kk) {
             constexpr int k = kk;
-            r2r_fwd_emit<T, L>(out, sep, tab, a.has_tw, k, v[k], v[(L - k) & (L - 1)]);
+            cplx<T> s, d;
+            real_sd<T>(v[k], v[(L - k) & (L - 1)], s, d);
+            r2r_fwd_emit<T, L>(out, sep, tab, a.has_tw, k, s, d);
         });
     } else {
         T yr[2 * L];
@@ -207,10 +195,7 @@ __global__ void __launch_bounds__(256) r2r_row_small_kernel(const TileArgs a) {
         });
         Dft<L, T>::run(v);
         static_for<L>([&](auto jj) {
-            constexpr int j = jj;
-            constexpr int p0 = 2 * j, p1 = 2 * j + 1;
-            constexpr int s0 = p0 < L ? 2 * p0 : 2 * (2 * L - 1 - p0) + 1;
-            constexpr int s1 = p1 < L ? 2 * p1 : 2 * (2 * L - 1 - p1) + 1;
+            constexpr int j = jj, s0 = r2r_perm(L, 2 * j), s1 = r2r_perm(L, 2 * j + 1);
             out[s0] = (s0 & 1) ? so * v[j].x : v[j].x;
             out[s1] = (s1 & 1) ? -so * v[j].y : -v[j].y;
         });
@@ -222,18 +207,13 @@ template <typename T, int L>
 static inline int launch_r2r_row(const TileArgs* a, int inverse, hipStream_t s, int query_only) {
     using S = Row2Shape<T, L>;
     static_assert(!S::HALF, "r2r rows have no half-width exchange");
-    return launch_groups(a, &TileArgs::total, S::W, query_only, [&](dim3 grid) {
-        if (inverse) hipLaunchKernelGGL((r2r_row_inv_kernel<T, L, S::W, S::NT, S::OCC, typename S::RL>), grid, dim3(S::NT), 0, s, *a);
-        else hipLaunchKernelGGL((r2r_row_fwd_kernel<T, L, S::W, S::NT, S::OCC, typename S::RL>), grid, dim3(S::NT), 0, s, *a);
-    });
+    return launch_row_pair(r2r_row_fwd_kernel<T, L, S::W, S::NT, S::OCC, typename S::RL>,
+                           r2r_row_inv_kernel<T, L, S::W, S::NT, S::OCC, typename S::RL>, S::W, S::NT, a, inverse, s, query_only);
 }
 
 template <typename T, int L>
 static inline int launch_r2r_row_small(const TileArgs* a, int inverse, hipStream_t s, int query_only) {
-    return launch_groups(a, &TileArgs::total, 256, query_only, [&](dim3 grid) {
-        if (inverse) hipLaunchKernelGGL((r2r_row_small_kernel<T, L, true>), grid, dim3(256), 0, s, *a);
-        else hipLaunchKernelGGL((r2r_row_small_kernel<T, L, false>), grid, dim3(256), 0, s, *a);
-    });
+    return launch_row_pair(r2r_row_small_kernel<T, L, false>, r2r_row_small_kernel<T, L, true>, 256, 256, a, inverse, s, query_only);
 }
 
 }  // namespace mifft

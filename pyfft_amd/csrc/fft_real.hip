@@ -3,6 +3,8 @@
 // shape (..., L) with L = nx / 2; Z = FFT(z) over all axes.  With k = (kp, kx) and -k = (-kp mod np, (L - kx) mod L) over ALL axes:
 //   forward  X[kp, kx] = 1/2 (Z[k] + conj Z[-k]) - 1/2 i w(nx)^kx (Z[k] - conj Z[-k]),          0 <= kx <= L   (half spectrum)
 //   inverse  Z[kp, kx] = (X[k] + conj X'[k]) + i w(nx)^-kx (X[k] - conj X'[k]),  X'[k] = X[-kp, L - kx],  0 <= kx < L
+// (fft_real_ident.hpp holds both as functions of s = a + conj b, d = a - conj b of a point a and its mirror b, for this file and the
+// one-launch rows: forward 1/2 (s - i w d), and 1/2 (s + i d) at kx = L from the pair of kx = 0, w(nx)^L = -1; inverse s + i conj(w) d)
 // and the unnormalised inverse complex transform of that Z is the unnormalised inverse real transform, packed the same way.  The inverse
 // reads the two edge planes kx = 0 and kx = L through their Hermitian parts 1/2 (X[kp, e] + conj X[-kp, e]): the leading axes' inverse
 // transforms of a non-Hermitian edge plane would otherwise leave imaginary parts that a real result has to drop (what numpy's irfftn
@@ -13,6 +15,7 @@
 // the L2 / Infinity Cache behind the first.
 #include <hip/hip_runtime.h>
 #include "mifft_internal.h"
+#include "fft_real_ident.hpp"
 
 namespace {
 
@@ -57,14 +60,13 @@ __global__ void __launch_bounds__(256) real_post_kernel(const RealPostArgs a) {
         const cx<T> p = zi[(long long)r * L + (kx & (L - 1))];
         const cx<T> q = zi[mrow * L + ((L - kx) & (L - 1))];
         const cx<T> w = tw[kx];
-        const cx<T> sm = {p.x + q.x, p.y - q.y};            // Z[k] + conj Z[-k]
-        const cx<T> df = {p.x - q.x, p.y + q.y};            // Z[k] - conj Z[-k]
-        const cx<T> t = {w.x * df.x - w.y * df.y, w.x * df.y + w.y * df.x};
+        cx<T> sm, df;
+        mifft::real_sd<T>(p, q, sm, df);                    // Z[k] + conj Z[-k], Z[k] - conj Z[-k]
         const T h = (T)0.5 * s;
-        cx<T> o = {(sm.x + t.y) * h, (sm.y - t.x) * h};     // 1/2 (sm - i t)
+        const cx<T> o = mifft::real_sep<T>(sm, w, df, h);
         cx<T>* xo = reinterpret_cast<cx<T>*>(a.out) + item * a.stride_out + (long long)r * (L + 1);
         xo[kx] = o;
-        if (kx == 0) xo[L] = cx<T>{(sm.x - df.y) * h, (sm.y + df.x) * h};   // the same two points, w(nx)^L = -1
+        if (kx == 0) xo[L] = mifft::real_sep_edge<T>(sm, df, h);   // the same two points
     } else {
         const cx<T>* xi = reinterpret_cast<const cx<T>*>(a.in) + item * a.stride_in;
         const int P = L + 1;
@@ -78,11 +80,10 @@ __global__ void __launch_bounds__(256) real_post_kernel(const RealPostArgs a) {
             q = cx<T>{(T)0.5 * (q.x + qm.x), (T)0.5 * (q.y - qm.y)};
         }
         const cx<T> w = tw[kx];
-        const cx<T> sm = {p.x + q.x, p.y - q.y};            // X[k] + conj X'[k]
-        const cx<T> df = {p.x - q.x, p.y + q.y};            // X[k] - conj X'[k]
-        const cx<T> t = {w.x * df.x + w.y * df.y, w.x * df.y - w.y * df.x};   // conj(w) * df
-        cx<T> o = {(sm.x - t.y) * s, (sm.y + t.x) * s};     // sm + i t
-        reinterpret_cast<cx<T>*>(a.out)[item * a.stride_out + (long long)r * L + kx] = o;
+        cx<T> sm, df;
+        mifft::real_sd<T>(p, q, sm, df);                    // X[k] + conj X'[k], X[k] - conj X'[k]
+        const cx<T> o = mifft::real_pack<T>(sm, w, df);
+        reinterpret_cast<cx<T>*>(a.out)[item * a.stride_out + (long long)r * L + kx] = cx<T>{o.x * s, o.y * s};
     }
 }
 

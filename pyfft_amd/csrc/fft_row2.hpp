@@ -268,13 +268,35 @@ struct Row2Stages<T, L, TPR, Ns, FIRST, HALF, RadixList<R, Rest...>, LAY, EPI, S
     }
 };
 
-// What the row kernels derive from (L, W, NT): TPR threads per row, PPT points per thread, LP = a row's padded LDS slab (row2_pad)
+// A thread's place in a row launch: c = which of the work-group's W rows (and LDS slabs), u = the lane within that row, row = the row's
+// index in the launch, valid = the row is inside the launch
+struct Row2Lane {
+    int c, u;
+    long long row;
+    bool valid;
+};
+
+// What the row kernels derive from (L, W, NT): TPR threads per row, PPT points per thread, LP = a row's padded LDS slab (row2_pad);
+// lane(total): the row preamble of every kernel on these stages, in a launch of `total` rows
 template <int L, int W, int NT> struct Row2Geom {
     static constexpr int TPR = NT / W;
     static constexpr int PPT = L / TPR;
     static constexpr int LP = L + L / 16;
     static_assert(TPR * W == NT && PPT * TPR == L && L >= 16, "bad row configuration");
+    static __device__ __forceinline__ Row2Lane lane(long long total) {
+        const int c = W == 1 ? 0 : threadIdx.x / TPR, u = W == 1 ? threadIdx.x : threadIdx.x % TPR;
+        const long long row = (long long)blockIdx.x * W + c;
+        return {c, u, row, row < total};
+    }
 };
+
+// W > 1: the row differs across the wave, so the thread's byte offset within its row goes into its own 64-bit bases and voff is 0
+template <int W, typename... P> __device__ __forceinline__ void row2_fold_offset(unsigned& voff, P&... base) {
+    if constexpr (W > 1) {
+        ((base += voff), ...);
+        voff = 0;
+    }
+}
 
 // OCC: waves per SIMD the register allocation must leave room for (1 = whatever the kernel needs)
 // TS = Complex32<T> (fft_tile.hpp): complex32 storage, interleaved (LAY 0), plain accesses
@@ -286,9 +308,8 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(OCC))) 
     constexpr int TPR = G::TPR, PPT = G::PPT, LP = G::LP;
     using LdsT = typename std::conditional<HALF, T, cplx<T>>::type;
     __shared__ __attribute__((aligned(16))) LdsT lds[W * LP];
-    const int c = W == 1 ? 0 : threadIdx.x / TPR, u = W == 1 ? threadIdx.x : threadIdx.x % TPR;
-    const long long row = (long long)blockIdx.x * W + c;
-    const bool valid = row < a.total;
+    const Row2Lane g = G::lane(a.total);
+    const long long row = g.row;
     // (planes: the row's first real / imaginary scalar; the thread's offset below counts complex numbers' bytes and is halved at the access)
     const char* inb = (LAY & 1) ? reinterpret_cast<const char*>(reinterpret_cast<const T*>(a.in0) + row * a.ostride_in)
                                 : reinterpret_cast<const char*>(reinterpret_cast<const cplx<ST>*>(a.in0) + row * a.ostride_in);
@@ -296,8 +317,8 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(OCC))) 
     char* outb = (LAY & 2) ? reinterpret_cast<char*>(reinterpret_cast<T*>(a.out0) + row * a.ostride_out)
                            : reinterpret_cast<char*>(reinterpret_cast<cplx<ST>*>(a.out0) + row * a.ostride_out);
     char* outb1 = (LAY & 2) ? reinterpret_cast<char*>(reinterpret_cast<T*>(a.out1) + row * a.ostride_out) : nullptr;
-    unsigned voff = (unsigned)u * (unsigned)sizeof(cplx<ST>);
-    if constexpr (W > 1) {  // the row differs across the wave: fold the thread's offset into its own 64-bit base
+    unsigned voff = (unsigned)g.u * (unsigned)sizeof(cplx<ST>);
+    if constexpr (W > 1) {  // row2_fold_offset, the planes at half the offset
         inb += (LAY & 1) ? voff / 2 : voff;
         if constexpr (LAY & 1) inb1 += voff / 2;
         outb += (LAY & 2) ? voff / 2 : voff;
@@ -305,7 +326,14 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(OCC))) 
         voff = 0;
     }
     cplx<T> v[PPT];
-    Row2Stages<T, L, TPR, 1, true, HALF, RL, LAY, void, ST>::run(lds + c * LP, v, a, u, inb, outb, voff, valid, nullptr, false, inb1, outb1);
+    Row2Stages<T, L, TPR, 1, true, HALF, RL, LAY, void, ST>::run(lds + g.c * LP, v, a, g.u, inb, outb, voff, g.valid, nullptr, false, inb1, outb1);
+}
+
+// The forward or the inverse kernel of a pair, one work-group of `nt` threads per `per_group` rows (the real and the cosine / sine rows)
+static inline int launch_row_pair(void (*fwd)(const TileArgs), void (*inv)(const TileArgs), int per_group, int nt, const TileArgs* a,
+                                  int inverse, hipStream_t s, int query_only) {
+    return launch_groups(a, &TileArgs::total, per_group, query_only,
+                         [&](dim3 grid) { hipLaunchKernelGGL(inverse ? inv : fwd, grid, dim3(nt), 0, s, *a); });
 }
 
 // TS, L: the shape is Row2Shape's (fft_row_shapes.hpp) for the working precision of TS

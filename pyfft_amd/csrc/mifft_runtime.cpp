@@ -537,6 +537,9 @@ int fill_ctl(mifft::FusedCtl* c, const mifft_fused_sync* sync, long long outer, 
     return 0;
 }
 
+// the f32 or the f64 dispatcher of an extension row family (real, convolution, cosine / sine rows)
+template <typename F> F* row_dispatcher(int32_t precision, F* f32, F* f64) { return precision == MIFFT_F64 ? f64 : f32; }
+
 }  // namespace
 
 extern "C" {
@@ -1329,8 +1332,7 @@ int mifft_launch_real_post(const mifft_real_post* d, mifft_stream_t stream) {
 }
 int mifft_real_row_supported(int32_t precision, int32_t n) {
     if (bad_precision(precision) || n < 4 || !is_pow2(n)) return MIFFT_E_UNSUPPORTED;
-    const int rc = precision == MIFFT_F64 ? mifft_real_row_dispatch_f64(n / 2, 0, nullptr, nullptr, 1)
-                                          : mifft_real_row_dispatch_f32(n / 2, 0, nullptr, nullptr, 1);
+    const int rc = row_dispatcher(precision, mifft_real_row_dispatch_f32, mifft_real_row_dispatch_f64)(n / 2, 0, nullptr, nullptr, 1);
     return rc == 0 ? 0 : MIFFT_E_UNSUPPORTED;
 }
 int mifft_launch_real_row(int32_t precision, int32_t n, int32_t inverse, int64_t rows, const void* in, void* out, const void* tw_half,
@@ -1356,8 +1358,7 @@ int mifft_launch_real_row(int32_t precision, int32_t n, int32_t inverse, int64_t
     a.total = rows;
     a.inverse = inverse;
     a.scale = scale;
-    const int rc = precision == MIFFT_F64 ? mifft_real_row_dispatch_f64((int)L, inverse, &a, (hipStream_t)stream, 0)
-                                          : mifft_real_row_dispatch_f32((int)L, inverse, &a, (hipStream_t)stream, 0);
+    const int rc = row_dispatcher(precision, mifft_real_row_dispatch_f32, mifft_real_row_dispatch_f64)((int)L, inverse, &a, (hipStream_t)stream, 0);
     if (rc == -2) return set_err(MIFFT_E_UNSUPPORTED, "real row: no kernel for n = %d", n);
     return launched(rc);
 }
@@ -1366,8 +1367,7 @@ int mifft_conv_row_supported(int32_t precision, int32_t real, int32_t n) {
     if (bad_precision(precision) || (real != 0 && real != 1) || n < 2 || !is_pow2(n)) return MIFFT_E_UNSUPPORTED;
     if (real && n < 4) return MIFFT_E_UNSUPPORTED;
     const int L = real ? n / 2 : n;
-    const int rc = precision == MIFFT_F64 ? mifft_conv_row_dispatch_f64(real, L, nullptr, nullptr, 1)
-                                          : mifft_conv_row_dispatch_f32(real, L, nullptr, nullptr, 1);
+    const int rc = row_dispatcher(precision, mifft_conv_row_dispatch_f32, mifft_conv_row_dispatch_f64)(real, L, nullptr, nullptr, 1);
     return rc == 0 ? 0 : MIFFT_E_UNSUPPORTED;
 }
 int mifft_launch_conv_row(int32_t precision, int32_t real, int32_t n, int64_t rows, const void* in, void* out, const void* spectrum,
@@ -1401,8 +1401,7 @@ int mifft_launch_conv_row(int32_t precision, int32_t real, int32_t n, int64_t ro
     a.spec_pitch = spectrum_pitch;
     a.correlate = correlate;
     a.scale = scale;
-    const int rc = precision == MIFFT_F64 ? mifft_conv_row_dispatch_f64(real, (int)L, &a, (hipStream_t)stream, 0)
-                                          : mifft_conv_row_dispatch_f32(real, (int)L, &a, (hipStream_t)stream, 0);
+    const int rc = row_dispatcher(precision, mifft_conv_row_dispatch_f32, mifft_conv_row_dispatch_f64)(real, (int)L, &a, (hipStream_t)stream, 0);
     if (rc == -2) return set_err(MIFFT_E_UNSUPPORTED, "conv row: no kernel for n = %d", n);
     return launched(rc);
 }
@@ -1455,8 +1454,7 @@ static int r2r_step(const mifft_r2r_step* d, int post, mifft_stream_t stream) {
 // one-launch cosine / sine rows (fft_r2r_row.hpp): rows of n reals, L = n / 2 packed points
 int mifft_r2r_row_supported(int32_t precision, int32_t n) {
     if (bad_precision(precision) || n < 4 || !is_pow2(n)) return MIFFT_E_UNSUPPORTED;
-    const int rc = precision == MIFFT_F64 ? mifft_r2r_row_dispatch_f64(n / 2, 0, nullptr, nullptr, 1)
-                                          : mifft_r2r_row_dispatch_f32(n / 2, 0, nullptr, nullptr, 1);
+    const int rc = row_dispatcher(precision, mifft_r2r_row_dispatch_f32, mifft_r2r_row_dispatch_f64)(n / 2, 0, nullptr, nullptr, 1);
     return rc == 0 ? 0 : MIFFT_E_UNSUPPORTED;
 }
 int mifft_launch_r2r_row(int32_t precision, int32_t n, int32_t inverse, int32_t kind, int64_t rows, const void* in, void* out,
@@ -1486,8 +1484,7 @@ int mifft_launch_r2r_row(int32_t precision, int32_t n, int32_t inverse, int32_t 
     a.total = rows;
     a.inverse = inverse;
     a.scale = 1.0;
-    const int rc = precision == MIFFT_F64 ? mifft_r2r_row_dispatch_f64(n / 2, inverse, &a, (hipStream_t)stream, 0)
-                                          : mifft_r2r_row_dispatch_f32(n / 2, inverse, &a, (hipStream_t)stream, 0);
+    const int rc = row_dispatcher(precision, mifft_r2r_row_dispatch_f32, mifft_r2r_row_dispatch_f64)(n / 2, inverse, &a, (hipStream_t)stream, 0);
     if (rc == -2) return set_err(MIFFT_E_UNSUPPORTED, "r2r row: no kernel for n = %d", n);
     return launched(rc);
 }
