@@ -539,6 +539,25 @@ int mifft_launch_conv_row(int32_t precision, int32_t real, int32_t n, int64_t ro
 int mifft_aux_mul_spectrum(int32_t precision, void *data, const void *spectrum, int64_t items, int64_t points, int64_t spectrum_pitch,
                            int32_t correlate, double scale, mifft_stream_t stream);
 
+/* Overlap-save FIR rows (docs/extensions.md "FIR filtering plans"): y[i][t] = scale * sum_j h[j] x[i][t - j], 0 <= t < length, x[i][< 0] = 0,
+ * for `items` signals in ONE launch and without scratch.  Every block of n points (real = 1: n reals) runs as a convolution row
+ * (transform, product with `spectrum`, unnormalised inverse: the caller folds 1 / n into scale); block r of an item starts at element
+ * r * hop - overlap of the item, hop = n - overlap, takes zeros outside [0, length) and stores its elements overlap .. n - 1 that fall
+ * inside [0, length).  No address outside [i * pitch, i * pitch + length) of either side is accessed.  overlap, length and pitch count
+ * elements (complex numbers; real = 1: reals): 0 <= overlap <= n / 2 (the filter has at most overlap + 1 taps), length >= 1,
+ * pitch >= length; real = 1: overlap and pitch even (length may be odd).  spectrum: the n (real = 1: n / 2 + 1) point spectrum of the
+ * zero-padded taps; spectrum_pitch: complex numbers between the spectra of consecutive ITEMS, 0 = one shared by all; it must not
+ * overlap in or out and is never written.  in and out must not overlap.  tw, tw_sep: as for mifft_launch_conv_row.  Bases aligned to
+ * one complex number (real data: one pair of reals).
+ *   mifft_fir_row_supported   0 if a kernel exists for (precision, real, n), else MIFFT_E_UNSUPPORTED
+ *   mifft_launch_fir_pad      out[f][j] = j < taps ? in[f * taps + j] : 0, j < n: `filters` filters of `taps` elements (complex numbers;
+ *                             real = 1: reals) zero-padded to n each; out 16-byte aligned, in aligned to one element, no overlap */
+int mifft_fir_row_supported(int32_t precision, int32_t real, int32_t n);
+int mifft_launch_fir_row(int32_t precision, int32_t real, int32_t n, int32_t overlap, int64_t length, int64_t pitch, int64_t items, const void *in,
+                         void *out, const void *spectrum, int64_t spectrum_pitch, const void *tw, const void *tw_sep, double scale,
+                         mifft_stream_t stream);
+int mifft_launch_fir_pad(int32_t precision, int32_t real, int32_t n, int32_t taps, int64_t filters, const void *in, void *out, mifft_stream_t stream);
+
 /* Cosine and sine transforms (docs/extensions.md "Real-to-real transforms"): DCT-II / DST-II forward and DCT-III / DST-III inverse
  * (scipy.fft's type 2 and 3) by Makhoul's algorithm, composed as pre step -> complex transform of the packed data -> post step.  An
  * item is a dense real array of shape n[0 .. ndim - 1] (numpy order, the last axis contiguous; every axis a power of two >= 2); v, its

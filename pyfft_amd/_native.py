@@ -253,6 +253,10 @@ PROTOTYPES = {
     "mifft_launch_real_row": (ctypes.c_int, [_i32, _i32, _i32, ctypes.c_int64, _vp, _vp, _vp, _vp, ctypes.c_double, _vp]),
     "mifft_conv_row_supported": (ctypes.c_int, [_i32, _i32, _i32]),
     "mifft_launch_conv_row": (ctypes.c_int, [_i32, _i32, _i32, ctypes.c_int64, _vp, _vp, _vp, ctypes.c_int64, _i32, _vp, _vp, ctypes.c_double, _vp]),
+    "mifft_fir_row_supported": (ctypes.c_int, [_i32, _i32, _i32]),
+    "mifft_launch_fir_row": (ctypes.c_int, [_i32, _i32, _i32, _i32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _vp, ctypes.c_int64, _vp, _vp,
+                                             ctypes.c_double, _vp]),
+    "mifft_launch_fir_pad": (ctypes.c_int, [_i32, _i32, _i32, _i32, ctypes.c_int64, _vp, _vp, _vp]),
     "mifft_aux_mul_spectrum": (ctypes.c_int, [_i32, _vp, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _i32, ctypes.c_double, _vp]),
     "mifft_launch_r2r_pre": (ctypes.c_int, [ctypes.POINTER(MifftR2rStep), _vp]),
     "mifft_launch_r2r_post": (ctypes.c_int, [ctypes.POINTER(MifftR2rStep), _vp]),

@@ -54,18 +54,19 @@ template <typename T> __device__ __forceinline__ cplx<T> conv_spec(const TileArg
 __device__ __forceinline__ void conv_group_fence() { __builtin_amdgcn_sched_barrier(0); }
 
 // The inverse transform of the registers (already in its first-stage layout) with the final stores.  voff: the thread's byte offset
-// within the row (0 where the kernel folded it into outb).
-template <typename T, int L, int W, bool HALF, typename RL, int TPR, typename LdsT>
+// within the row (0 where the kernel folded it into outb).  STORE: the EPI of the inverse's last stage (fft_fir_row.hpp: the masked
+// stores of an overlap-save block); void: the plain stores.
+template <typename T, int L, int W, bool HALF, typename RL, int TPR, typename STORE = void, typename LdsT>
 __device__ __forceinline__ void conv_inverse(LdsT* lds, cplx<T>* v, const TileArgs& a, int tid, char* outb, bool valid) {
     using Inv = typename ReverseRadices<RL>::type;
     TileArgs c = a;
     c.inverse = 1;
     const unsigned voff = W > 1 ? 0u : (unsigned)tid * (unsigned)sizeof(cplx<T>);
     __syncthreads();       // every thread is done with the slab (the forward's last operands, the mirrors): the inverse may spill
-    Row2Stages<T, L, TPR, 1, true, HALF, Inv>::template run<true>(lds, v, c, tid, nullptr, outb, voff, valid);
+    Row2Stages<T, L, TPR, 1, true, HALF, Inv, 0, STORE>::template run<true>(lds, v, c, tid, nullptr, outb, voff, valid);
 }
 
-template <typename T, int L, int W, bool HALF, typename RL> struct ConvEpi {
+template <typename T, int L, int W, bool HALF, typename RL, typename STORE = void> struct ConvEpi {
     template <int NB, int R, int TPR, int LR, typename LdsT>
     static __device__ __forceinline__ void run(LdsT* lds, cplx<T>* v, const TileArgs& a, int tid, char* outb, bool valid) {
         static_assert(FirstRadix<typename ReverseRadices<RL>::type>::value == R, "the inverse starts with the forward's last radix");
@@ -76,7 +77,7 @@ template <typename T, int L, int W, bool HALF, typename RL> struct ConvEpi {
             });
             conv_group_fence();
         });
-        conv_inverse<T, L, W, HALF, RL, TPR>(lds, v, a, tid, outb, valid);
+        conv_inverse<T, L, W, HALF, RL, TPR, STORE>(lds, v, a, tid, outb, valid);
     }
 };
 
@@ -98,7 +99,7 @@ __device__ __forceinline__ cplx<T> conv_real_pair(cplx<T> s, cplx<T> d, int idx,
     return real_pack<T>(sm, w, df);
 }
 
-template <typename T, int L, int W, bool HALF, typename RL> struct ConvRealEpi {
+template <typename T, int L, int W, bool HALF, typename RL, typename STORE = void> struct ConvRealEpi {
     template <int NB, int R, int TPR, int LR, typename LdsT>
     static __device__ __forceinline__ void run(LdsT* lds, cplx<T>* v, const TileArgs& a, int tid, char* outb, bool valid) {
         static_assert(FirstRadix<typename ReverseRadices<RL>::type>::value == R, "the inverse starts with the forward's last radix");
@@ -107,7 +108,7 @@ template <typename T, int L, int W, bool HALF, typename RL> struct ConvRealEpi {
             v[i] = conv_real_pair<T, L>(s, d, idx, a, valid);
             conv_group_fence();
         });
-        conv_inverse<T, L, W, HALF, RL, TPR>(lds, v, a, tid, outb, valid);
+        conv_inverse<T, L, W, HALF, RL, TPR, STORE>(lds, v, a, tid, outb, valid);
     }
 };
 

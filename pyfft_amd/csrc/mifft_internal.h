@@ -86,6 +86,13 @@ int mifft_real_row_dispatch_f64(int L, int inverse, const mifft::TileArgs* a, hi
 namespace mifft { struct ConvRowArgs; }
 int mifft_conv_row_dispatch_f32(int real, int L, const mifft::ConvRowArgs* a, hipStream_t s, int query_only);
 int mifft_conv_row_dispatch_f64(int real, int L, const mifft::ConvRowArgs* a, hipStream_t s, int query_only);
+// fft_fir_f32.hip / _f64.hip: one-launch overlap-save FIR rows, blocks of L complex (real: packed) points; 0 launched (query: a kernel
+// exists), -2 none, -1 grid too large.  mifft_fir_pad_launch: out[f][j] = j < taps ? in[f * taps + j] : 0, j < n, in scalars of the
+// precision, n a multiple of 16 bytes' worth, out 16-byte aligned
+namespace mifft { struct FirRowArgs; }
+int mifft_fir_row_dispatch_f32(int real, int L, const mifft::FirRowArgs* a, hipStream_t s, int query_only);
+int mifft_fir_row_dispatch_f64(int real, int L, const mifft::FirRowArgs* a, hipStream_t s, int query_only);
+int mifft_fir_pad_launch(int f64, const void* in, void* out, long long filters, int n, int taps, hipStream_t s);
 // fft_nd2z.hip: 0 = launched (query 1: a kernel exists; query 2: one that is preferred at every buffer size), -2 = none, -1 = grid too large
 int mifft_nd2z(int f64, int x, int y, int z, const mifft::TileArgs* a, hipStream_t s, int query);
 // fft_half.hip / fft_nd2_c32_*.hip: complex32 twins of the fp32 one-launch kernels; 0 launched (query: a kernel exists), -2 none, -1 grid too large

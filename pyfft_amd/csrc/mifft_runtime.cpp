@@ -14,6 +14,7 @@
 #include "../../include/mifft.h"
 #include "mifft_internal.h"
 #include "fft_conv_row.hpp"
+#include "fft_fir_row.hpp"
 
 namespace {
 
@@ -1404,6 +1405,71 @@ int mifft_launch_conv_row(int32_t precision, int32_t real, int32_t n, int64_t ro
     const int rc = row_dispatcher(precision, mifft_conv_row_dispatch_f32, mifft_conv_row_dispatch_f64)(real, (int)L, &a, (hipStream_t)stream, 0);
     if (rc == -2) return set_err(MIFFT_E_UNSUPPORTED, "conv row: no kernel for n = %d", n);
     return launched(rc);
+}
+// overlap-save FIR rows (fft_fir_row.hpp): blocks of n complex points (L = n) or n reals (L = n / 2 packed points)
+int mifft_fir_row_supported(int32_t precision, int32_t real, int32_t n) {
+    if (bad_precision(precision) || (real != 0 && real != 1) || n < 4 || !is_pow2(n)) return MIFFT_E_UNSUPPORTED;
+    const int rc = row_dispatcher(precision, mifft_fir_row_dispatch_f32, mifft_fir_row_dispatch_f64)(real, real ? n / 2 : n, nullptr, nullptr, 1);
+    return rc == 0 ? 0 : MIFFT_E_UNSUPPORTED;
+}
+int mifft_launch_fir_row(int32_t precision, int32_t real, int32_t n, int32_t ov, int64_t length, int64_t pitch, int64_t items, const void* in,
+                         void* out, const void* spectrum, int64_t spectrum_pitch, const void* tw, const void* tw_sep, double scale,
+                         mifft_stream_t stream) {
+    if (bad_precision(precision)) return set_err(MIFFT_E_INVALID, "fir row: bad precision %d", precision);
+    if (real != 0 && real != 1) return set_err(MIFFT_E_INVALID, "fir row: real must be 0 or 1");
+    if (n < 4 || !is_pow2(n)) return set_err(MIFFT_E_INVALID, "fir row: n = %d is not a power of two >= 4", n);
+    if (mifft_fir_row_supported(precision, real, n) != 0) return set_err(MIFFT_E_UNSUPPORTED, "fir row: no kernel for n = %d", n);
+    if (ov < 0 || ov > n / 2 || (real && (ov & 1)))
+        return set_err(MIFFT_E_INVALID, "fir row: overlap %d is not in 0 .. n / 2%s", ov, real ? ", or is odd" : "");
+    if (length < 1) return set_err(MIFFT_E_INVALID, "fir row: length must be at least 1");
+    if (pitch < length || (real && (pitch & 1))) return set_err(MIFFT_E_INVALID, "fir row: pitch %lld is below the length%s", (long long)pitch, real ? ", or is odd" : "");
+    if (items < 0) return set_err(MIFFT_E_INVALID, "fir row: negative item count");
+    if (!in || !out || !spectrum || !tw || (real && !tw_sep)) return set_err(MIFFT_E_INVALID, "fir row: null buffer");
+    const long long esz = complex_bytes(precision), ssz = real ? esz / 2 : esz;     // a point (real: one pair), an element
+    if (misaligned_complex(precision, {in, out, spectrum, tw, tw_sep}))
+        return set_err(MIFFT_E_INVALID, "fir row: buffers must be aligned to one complex number (real data: one pair)");
+    const long long L = real ? n / 2 : n, sp = real ? L + 1 : L, hop = n - ov, blocks = (length + hop - 1) / hop;
+    if (spectrum_pitch != 0 && spectrum_pitch < sp)
+        return set_err(MIFFT_E_INVALID, "fir row: spectrum_pitch %lld is neither 0 (shared) nor at least %lld", (long long)spectrum_pitch, sp);
+    if (mul3_checked(items, pitch, ssz) < 0 || mul3_checked(items, blocks, n) < 0 || mul3_checked(items, spectrum_pitch > sp ? spectrum_pitch : sp, esz) < 0)
+        return set_err(MIFFT_E_INVALID, "fir row: items * pitch overflows");
+    if (items == 0) return 0;
+    const uintptr_t bytes = (uintptr_t)(((items - 1) * pitch + length) * ssz), sbytes = (uintptr_t)(((spectrum_pitch ? (items - 1) * spectrum_pitch : 0) + sp) * esz);
+    if (overlap(in, bytes, out, bytes)) return set_err(MIFFT_E_INVALID, "fir row: input and output overlap (out of place only)");
+    if (overlap(spectrum, sbytes, in, bytes) || overlap(spectrum, sbytes, out, bytes)) return set_err(MIFFT_E_INVALID, "fir row: the spectrum overlaps the data");
+    mifft::FirRowArgs a = {};
+    a.in = in;
+    a.out = out;
+    a.spec = spectrum;
+    a.tw = tw;
+    a.tw_sep = tw_sep;
+    a.rows = items * blocks;
+    a.blocks = blocks;
+    a.pitch = real ? pitch / 2 : pitch;
+    a.length = length;
+    a.spec_pitch = spectrum_pitch;
+    a.ov = real ? ov / 2 : ov;
+    a.scale = scale;
+    const int rc = row_dispatcher(precision, mifft_fir_row_dispatch_f32, mifft_fir_row_dispatch_f64)(real, (int)L, &a, (hipStream_t)stream, 0);
+    if (rc == -2) return set_err(MIFFT_E_UNSUPPORTED, "fir row: no kernel for n = %d", n);
+    return launched(rc);
+}
+int mifft_launch_fir_pad(int32_t precision, int32_t real, int32_t n, int32_t taps, int64_t filters, const void* in, void* out, mifft_stream_t stream) {
+    if (bad_precision(precision)) return set_err(MIFFT_E_INVALID, "fir pad: bad precision %d", precision);
+    if (real != 0 && real != 1) return set_err(MIFFT_E_INVALID, "fir pad: real must be 0 or 1");
+    if (n < 4 || !is_pow2(n)) return set_err(MIFFT_E_INVALID, "fir pad: n = %d is not a power of two >= 4", n);
+    if (taps < 1 || taps > n) return set_err(MIFFT_E_INVALID, "fir pad: taps = %d is not in 1 .. n", taps);
+    if (filters < 0) return set_err(MIFFT_E_INVALID, "fir pad: negative filter count");
+    if (!in || !out) return set_err(MIFFT_E_INVALID, "fir pad: null buffer");
+    const long long esz = real ? complex_bytes(precision) / 2 : complex_bytes(precision);
+    if (misaligned((uintptr_t)esz - 1, {in}) || misaligned(15, {out}))
+        return set_err(MIFFT_E_INVALID, "fir pad: the taps must be aligned to one element, the output to 16 bytes");
+    if (mul3_checked(filters, n, esz) < 0) return set_err(MIFFT_E_INVALID, "fir pad: filters * n overflows");
+    if (filters == 0) return 0;
+    if (overlap(in, (uintptr_t)(filters * taps * esz), out, (uintptr_t)(filters * n * esz)))
+        return set_err(MIFFT_E_INVALID, "fir pad: input and output overlap (out of place only)");
+    const int sc = real ? 1 : 2;
+    return launched(mifft_fir_pad_launch(precision == MIFFT_F64, in, out, filters, n * sc, taps * sc, (hipStream_t)stream));
 }
 int mifft_aux_mul_spectrum(int32_t precision, void* data, const void* spectrum, int64_t items, int64_t points, int64_t spectrum_pitch,
                            int32_t correlate, double scale, mifft_stream_t stream) {

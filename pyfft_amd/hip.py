@@ -608,6 +608,11 @@ def Plan(*args, **kwds):
     (spectrum_batch=batch).  y may be x (in place).  With real=True, y == numpy.fft.irfftn(numpy.fft.rfftn(x) * S, s=shape) * scale (numpy's
     edge-plane rule).  filter_spectrum(h, H) computes H = fftn(h) (rfftn), scale 1.  complex64 / complex128 or real=True float32 / float64;
     complex32, split planes, any_size= and parent_shape= are ValueErrors.
+    `convolve=True, taps=m`: overlap-save FIR filtering (pyfft_amd/fir.py): `shape` is the block length n (1-D, a power of two with a
+    one-launch instance), 1 <= m <= n / 2; execute(x, y, spectrum=H, length=Lx, batch=k, pitch=None, spectrum_batch=1) computes
+    y[i, t] = scale * sum_{j<m} h[j] x[i, t - j], 0 <= t < Lx, for k signals of any length Lx in ONE launch without scratch, out of place
+    only; filter_spectrum(h, H) computes H = fft(h zero-padded to n) (rfft with real=True).  The plan has overlap, hop, blocks(length),
+    kernel and fir_form.  correlate=True, N-D shapes, complex32, r2r=, any_size= and parent_shape= are ValueErrors naming taps.
     `r2r="dct"` / `"dst"`: cosine / sine transforms (pyfft_amd/r2r.py): float32 / float64 real data, prod(shape) per item; execute(x, y)
     == scipy.fft.dctn(x, type=2) * scale (dstn for "dst"), execute(y, x, inverse=True) == idctn(y, type=2) / scale (normalize=False:
     dctn(y, type=3) / scale); `ortho=True` is norm="ortho" both ways; y may be x (in place).  Complex dtypes, real=, convolve=, any_size=
@@ -630,6 +635,17 @@ def Plan(*args, **kwds):
     convolve = bool(kwds.pop('convolve', False))
     # opt-in cosine / sine transforms (pyfft_amd/r2r.py): r2r="dct" | "dst", ortho=True for norm="ortho"
     r2r = kwds.pop('r2r', None)
+    # opt-in overlap-save FIR plans (pyfft_amd/fir.py): convolve=True with taps=m, the shape is the block length
+    taps = kwds.pop('taps', None)
+    if taps is not None:
+        if not convolve:
+            raise ValueError("pyfft_amd: taps= needs convolve=True")
+        if r2r is not None or any_size or parent_shape is not None:
+            raise ValueError("pyfft_amd: taps= cannot be combined with r2r=, any_size= or parent_shape=")
+        if kwds.pop('correlate', False):
+            raise ValueError("pyfft_amd: taps= plans have no correlate=True: reverse and conjugate the taps instead")
+        from .fir import FirPlan
+        FirPlan.validate(*args, real=real, taps=taps, **kwds)
     if r2r is not None:
         if real or convolve or any_size or parent_shape is not None:
             raise ValueError("pyfft_amd: r2r= cannot be combined with real=, convolve=, any_size= or parent_shape=")
@@ -698,6 +714,8 @@ def Plan(*args, **kwds):
     context = Context(device, stream_obj, mempool)
     prev = context.activate()       # context=i: tables and scratch are allocated on device i
     try:
+        if taps is not None:
+            return FirPlan(context, *args, real=real, taps=taps, **kwds)
         if convolve:
             from .conv import ConvPlan
             return ConvPlan(context, *args, real=real, **kwds)
