@@ -327,10 +327,10 @@ int mifft_launch_chain_pipelined(const mifft_pass *passes, int32_t npasses, void
  * Fused form of a two-pass long contiguous axis N = p0->L * p1->L: both Stockham passes of all `p0->outer` transforms in
  * ONE persistent launch, pass 1 of transform t trailing pass 0 by `lag` transforms, with the intermediate in a scratch
  * ring of `ring_slots` transforms (ring_slots > lag) that stays in the Infinity Cache.
- *   shapes    fp32: p0->L, p1->L in {256, 512, 1024}, or 2048 x 2048 / 2048 x 1024; fp64: 1024 x 1024.
- *             1-D form: p0 = the transposing first pass (COL, S == 1, M == p1->L), p1 = the plain strided last pass
- *             (COL, M == 1, S == p0->L).  2-D form (the squares 512 / 1024 / 2048 in fp32, 1024 in fp64): p0 = the ROW
- *             pass, p1 = the strided COL pass of the plan.  Anything else: MIFFT_E_UNSUPPORTED.
+ *   shapes    1-D form: p0 = the transposing first pass (COL, S == 1, M == p1->L), p1 = the plain strided last pass
+ *             (COL, M == 1, S == p0->L).  2-D form: p0 = the ROW pass, p1 = the strided COL pass of the plan.  Which lengths
+ *             have a kernel, per precision and layout: mifft_fused2_kernel below (the table of forms is in docs/persistent.md).
+ *             Anything else: MIFFT_E_UNSUPPORTED.
  *   sync      counters + error word, see mifft_fused_sync below (one 256-byte line per counter, csrc/fft_fused2.hpp).  After
  *             completion a non-zero error word reports a dependency time-out (results invalid).
  *   ring      always interleaved (ring0; ring1 is ignored), also for split-plane in/out buffers.
@@ -358,10 +358,29 @@ typedef struct mifft_fused_sync {
     void *counters_next;
     void *error_word;
 } mifft_fused_sync;
-/* 1 <= lag < ring_slots, MIFFT_E_INVALID otherwise */
+/* 1 <= lag < ring_slots, MIFFT_E_INVALID otherwise.  A pair of descriptors without a kernel (mifft_fused2_kernel below) is refused
+ * BEFORE `sync` is looked at: such a call neither validates the sync block nor zeroes a counter set, and a call with both a bad sync
+ * block and a shape without a kernel reports the shape. */
 int mifft_launch_fused2(const mifft_pass *p0, const mifft_pass *p1, const void *in0, const void *in1, void *out0,
                         void *out1, void *ring0, void *ring1, int32_t ring_slots, int32_t lag, const mifft_fused_sync *sync,
                         int32_t grid, mifft_stream_t stream);
+
+/* Which kernel form mifft_launch_fused2 runs for the two descriptors: a pure query (it never touches a device), the one selector the
+ * launch itself goes through.  The answer also depends on the calling thread's development switches.  Returns a MIFFT_FUSED2_KERNEL_*
+ * constant and, through tiles0 / tiles1 (either may be NULL), the work-list tiles per transform of the two passes; else the error code
+ * (with its message) mifft_launch_fused2 gives for the descriptors before it looks at a buffer.  docs/persistent.md has the table of
+ * forms, their work-groups, tile widths and shapes. */
+#define MIFFT_FUSED2_KERNEL_1D          1  /* 1-D, 256-thread tiles of 16 columns in both passes (fft_fused2_kernel) */
+#define MIFFT_FUSED2_KERNEL_1D_SIBLINGS 2  /* 1-D fp32 planes, two sibling 16-column tiles per 512-thread work-group (fft_fused2s_kernel) */
+#define MIFFT_FUSED2_KERNEL_1D_WIDE     3  /* 1-D fp32 interleaved, 256-thread tiles of 32 columns in both passes (fft_fused2w_kernel) */
+#define MIFFT_FUSED2_KERNEL_1D_MIXED    4  /* 1-D fp32 interleaved 1024 x 512: 16 columns, then 32 (fft_fused2m_kernel) */
+#define MIFFT_FUSED2_KERNEL_2D          5  /* 2-D as two transposing passes, 256-thread tiles of 16 columns (fft_fused2d_kernel) */
+#define MIFFT_FUSED2_KERNEL_2D_WIDE     6  /* ... fp32 interleaved, 32 columns in the pass of an axis <= 512 (fft_fused2dw_kernel) */
+#define MIFFT_FUSED2_KERNEL_1D_BIG      7  /* 1-D, 512-thread tiles of 16 columns (fft_fused3_kernel) */
+#define MIFFT_FUSED2_KERNEL_2D_BIG      8  /* 2-D as two transposing passes, 512-thread tiles of 16 columns (fft_fused3d_kernel) */
+#define MIFFT_FUSED2_KERNEL_2D_ROWFIRST 9  /* 2-D fp32 planes in the chain's order: groups of 16 rows, then 16-column tiles (fft_fused2r_kernel) */
+#define MIFFT_FUSED2_KERNEL_1D_CHAIN64  10 /* 1-D fp64 2048-point first pass, 1024-thread stage-chain tiles of 8 / 16 columns (fft_fusedx64_kernel) */
+int mifft_fused2_kernel(const mifft_pass *p0, const mifft_pass *p1, uint32_t *tiles0, uint32_t *tiles1);
 
 /*
  * Persistent form of a 3-D plan made of two PASS PAIRS (mifft_pair_split > 0): passes[0..3] = ROW x | COL y (R0) | COL y (R1) |

@@ -34,6 +34,9 @@ FLAG_WRITE_THROUGH = 32
 FLAG_PAIR_WITH_NEXT = 16
 HALF_KERNEL_TILE, HALF_KERNEL_ROW, HALF_KERNEL_ND2, HALF_KERNEL_ND = 1, 2, 3, 4    # mifft_half_kernel
 ND_KERNEL_WAVE, ND_KERNEL_ND2Z, ND_KERNEL_ND2, ND_KERNEL_ND2ZP, ND_KERNEL_ND2P, ND_KERNEL_ND2T, ND_KERNEL_ND = 1, 2, 3, 4, 5, 6, 7    # mifft_nd_kernel
+# mifft_fused2_kernel
+FUSED2_KERNEL_1D, FUSED2_KERNEL_1D_SIBLINGS, FUSED2_KERNEL_1D_WIDE, FUSED2_KERNEL_1D_MIXED, FUSED2_KERNEL_2D = 1, 2, 3, 4, 5
+FUSED2_KERNEL_2D_WIDE, FUSED2_KERNEL_1D_BIG, FUSED2_KERNEL_2D_BIG, FUSED2_KERNEL_2D_ROWFIRST, FUSED2_KERNEL_1D_CHAIN64 = 6, 7, 8, 9, 10
 FUSED2_COUNTER_STRIDE = 64          # MIFFT_FUSED2_COUNTER_STRIDE (uint32 words between two counters)
 
 
@@ -227,6 +230,7 @@ PROTOTYPES = {
     "mifft_launch_chain_pipelined": (ctypes.c_int, [_pass_p, _i32, _vpp, _vpp, ctypes.c_int64, ctypes.c_int64,
                                                       ctypes.c_int64, _vp, _vpp, _i32, _vpp]),
     "mifft_launch_fused2": (ctypes.c_int, [_pass_p, _pass_p, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _sync_p, _i32, _vp]),
+    "mifft_fused2_kernel": (ctypes.c_int, [_pass_p, _pass_p, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
     "mifft_fused_pair_supported": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32]),
     "mifft_fused_pair_split": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32]),
     "mifft_launch_fused_pair": (ctypes.c_int, [_pass_p, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _sync_p, _i32, _vp]),

@@ -31,13 +31,10 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) 
 }
 }  // namespace
 
-// tiles0 / tiles1 per transform; query != 0: nothing is launched
-extern "C" int mifft_fusedx_f64(int L0, int L1, const FusedArgs* f, unsigned grid, hipStream_t s, int query, unsigned* tiles0, unsigned* tiles1) {
-    if (L0 != 2048 || (L1 != 2048 && L1 != 1024)) return MIFFT_E_UNSUPPORTED;
-    if (tiles0) *tiles0 = (unsigned)L1 / 8u;
-    if (tiles1) *tiles1 = L1 == 2048 ? 256u : 128u;
-    if (query) return 0;
-    if (L1 == 2048) hipLaunchKernelGGL((fft_fusedx64_kernel<2048, 8, RadixList<16, 16, 8>>), dim3(grid), dim3(1024), 0, s, *f);
-    else hipLaunchKernelGGL((fft_fusedx64_kernel<1024, 16, RadixList<16, 8, 8>>), dim3(grid), dim3(1024), 0, s, *f);
-    return (int)hipGetLastError();
+// pass 0 over L1 / 8 column tiles, pass 1 over 2048 / W1
+extern "C" int mifft_fusedx_f64(int L0, int L1, int split, const FusedArgs* f, unsigned grid, hipStream_t s, int query, mifft_fused2_choice* c) {
+    if (split || L0 != 2048) return MIFFT_E_UNSUPPORTED;
+    if (L1 == 2048) MIFFT_FUSED2_RUN(MIFFT_FUSED2_KERNEL_1D_CHAIN64, 2048 / 8, 2048 / 8, 1024, fft_fusedx64_kernel<2048, 8, RadixList<16, 16, 8>>);
+    if (L1 == 1024) MIFFT_FUSED2_RUN(MIFFT_FUSED2_KERNEL_1D_CHAIN64, 1024 / 8, 2048 / 16, 1024, fft_fusedx64_kernel<1024, 16, RadixList<16, 8, 8>>);
+    return MIFFT_E_UNSUPPORTED;
 }

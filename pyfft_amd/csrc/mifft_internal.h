@@ -23,15 +23,19 @@ int mifft_nd2_f32_supported(int x, int y, int z);
 int mifft_nd2_f32_launch(int x, int y, int z, const mifft::TileArgs* a, hipStream_t s);
 int mifft_nd2_f64_supported(int x, int y, int z);
 int mifft_nd2_f64_launch(int x, int y, int z, const mifft::TileArgs* a, hipStream_t s);
-int mifft_fused2_f32_launch(int L0, int L1, const mifft::FusedArgs* f, int split, unsigned grid, hipStream_t s);
 void mifft_note_pair_lanes_form(int form);    // mifft_runtime.cpp: what mifft_debug_last_pair_lanes_form answers on this thread
-int mifft_fused2dw_f32(int ny, int nx, const mifft::FusedArgs* f, unsigned grid, hipStream_t s, int query, unsigned* tiles0, unsigned* tiles1);
-int mifft_fused2r_f32(int ny, int nx, const mifft::FusedArgs* f, unsigned grid, hipStream_t s, int query);
-int mifft_fused2w_f32_launch(int L0, int L1, const mifft::FusedArgs* f, unsigned grid, hipStream_t s);
-int mifft_fused2d_f32_launch(int ny, int nx, const mifft::FusedArgs* f, int split, unsigned grid, hipStream_t s);
-int mifft_fused3d_f64_launch(int ny, int nx, const mifft::FusedArgs* f, int split, unsigned grid, hipStream_t s);
-int mifft_fusedx_f64(int L0, int L1, const mifft::FusedArgs* f, unsigned grid, hipStream_t s, int query, unsigned* tiles0, unsigned* tiles1);
-int mifft_fused3_f64_launch(int L0, int L1, const mifft::FusedArgs* f, int split, unsigned grid, hipStream_t s);
+// The units of the persistent two-pass launch (docs/persistent.md has the table of forms).  Each answers from the instance list it
+// launches from, for (a, b) = (L0, L1) of a 1-D pair / (ny, nx) of a 2-D one and the layout of the user's buffers, under the calling
+// thread's development switches: the form (MIFFT_FUSED2_KERNEL_*) and the work-list tiles per transform go to *c, then -- query == 0 --
+// the kernel is launched.  0, MIFFT_E_UNSUPPORTED without such an instance, or a hipError_t.  The 2-D launchers of a precision
+// (mifft_fused2d_f32, mifft_fused3d_f64) answer 1 for a shape the 2-D form does not name at all.
+struct mifft_fused2_choice {
+    int form;
+    unsigned tiles0, tiles1;
+};
+typedef int mifft_fused2_unit(int a, int b, int split, const mifft::FusedArgs* f, unsigned grid, hipStream_t s, int query, mifft_fused2_choice* c);
+mifft_fused2_unit mifft_fused2r_f32, mifft_fused2dw_f32, mifft_fused2d_rect_f32, mifft_fused2d_f32, mifft_fused3d_f64;      // 2-D
+mifft_fused2_unit mifft_fused2w_f32, mifft_fused2_f32, mifft_fusedx_f64, mifft_fused3_f64;                                  // 1-D
 int mifft_aux_copy_launch(const struct mifft_copy* c, const void* s0, const void* s1, void* d0, void* d1, hipStream_t s);
 int mifft_aux_mul_rows_launch(int f64, void* a, const void* b, long long rows, long long n, hipStream_t s);
 // data[i][j] = scale * data[i][j] * S[i * spectrum_pitch + j] (S = conj(spectrum) when correlate); 0 launched, -1 grid too large
@@ -101,6 +105,15 @@ int mifft_c32_nd_launch(long long n, const mifft::NdArgs* a, hipStream_t s);
 int mifft_nd2_c32_supported(int x, int y, int z);
 int mifft_nd2_c32_launch(int x, int y, int z, const mifft::TileArgs* a, hipStream_t s);
 }
+
+// one row of a mifft_fused2_unit's instance list: the form and its tiles per transform, then the launch of the kernel on THREADS threads
+#define MIFFT_FUSED2_RUN(FORM, T0, T1, THREADS, ...)                             \
+    do {                                                                         \
+        *c = {FORM, (unsigned)(T0), (unsigned)(T1)};                             \
+        if (query) return 0;                                                     \
+        hipLaunchKernelGGL((__VA_ARGS__), dim3(grid), dim3(THREADS), 0, s, *f);  \
+        return (int)hipGetLastError();                                           \
+    } while (0)
 
 namespace mifft {
 template <typename T, int L, int W, int NT, bool ROW, bool TR, typename RL>

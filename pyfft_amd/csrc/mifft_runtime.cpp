@@ -495,6 +495,40 @@ bool mixed_rows_prefer_nd(bool f64, int n) {
 // keys 1, 4 and 11 are retired: they selected kernel forms this library no longer has (include/mifft.h)
 bool debug_key_ok(int key) { return key >= 0 && key < MIFFT_DEBUG_KEYS && key != 1 && key != 4 && key != 11; }
 
+// The kernel form of a persistent two-pass launch (mifft_fused2_kernel, mifft_launch_fused2): validates the two descriptors, then a
+// pure function of them and of the calling thread's development switches.  Which shapes have a kernel, and on which tiles, is asked
+// of the units -- each answers from the list it launches from (mifft_internal.h) -- in the order of preference; 0 with *c filled, or a
+// negative error code with its message.
+int select_fused2(const mifft_pass* p0, const mifft_pass* p1, mifft_fused2_choice* c) {
+    int rc = validate(p0);
+    if (!rc) rc = validate(p1);
+    if (rc) return rc;
+    if (p0->precision != p1->precision) return set_err(MIFFT_E_INVALID, "fused2: passes of two precisions");
+    const bool f64 = p0->precision == MIFFT_F64;
+    const int split = p0->layout == MIFFT_SPLIT ? 1 : 0;
+    auto has = [&](mifft_fused2_unit* unit, int a, int b) { return (rc = unit(a, b, split, nullptr, 0, nullptr, 1, c)) == 0; };
+    if (p0->kind == MIFFT_PASS_ROW) {
+        // 2-D form: the ROW pass (x axis, length nx) and the strided COL pass (y axis, length ny) of a 2-D plan: the row-first kernel,
+        // else two transposing column passes -- on 32-column tiles, else on the tiles of the precision's 2-D launcher
+        const int nx = p0->L, ny = p1->L;
+        const bool plan2d = p1->kind == MIFFT_PASS_COL && p1->S == nx && p1->M == 1 && p0->outer == p1->outer * ny &&
+                            p0->layout == p1->layout && p0->inverse == p1->inverse;
+        if (plan2d && (f64 ? has(mifft_fused3d_f64, ny, nx) : has(mifft_fused2r_f32, ny, nx) || has(mifft_fused2dw_f32, ny, nx) || has(mifft_fused2d_f32, ny, nx)))
+            return 0;
+        if (!plan2d || rc != MIFFT_E_UNSUPPORTED)
+            return set_err(MIFFT_E_UNSUPPORTED, "fused2: the 2-D form takes (ny, nx) in {512, 1024, 2048}^2 (fp32; interleaved: also a 256-point side next to one <= 1024; split planes: {256, 512, 1024}^2 and the 2048 square) / {256, 512, 1024}^2 (fp64; split planes: 1024 x 1024; 256 only next to <= 512)");
+    } else {
+        if (p0->kind != MIFFT_PASS_COL || p1->kind != MIFFT_PASS_COL || p0->S != 1 || p0->M != p1->L || p1->M != 1 ||
+            p1->S != p0->L || p0->outer != p1->outer || p0->layout != p1->layout || p0->inverse != p1->inverse)
+            return set_err(MIFFT_E_INVALID, "fused2: passes are not the two passes of one long contiguous axis");
+        // 32-column and mixed tiles, the fp64 stage-chain tiles, else the tiles of the precision's 1-D launcher
+        if (f64 ? has(mifft_fusedx_f64, p0->L, p1->L) || has(mifft_fused3_f64, p0->L, p1->L)
+                : has(mifft_fused2w_f32, p0->L, p1->L) || has(mifft_fused2_f32, p0->L, p1->L))
+            return 0;
+    }
+    return set_err(MIFFT_E_UNSUPPORTED, "fused2: no kernel for %d x %d", p0->L, p1->L);
+}
+
 // work-list control block of a persistent launch from the caller's mifft_fused_sync (include/mifft.h): validates, zeroes the
 // counters on `stream` when the caller does not alternate between two sets
 int fill_ctl(mifft::FusedCtl* c, const mifft_fused_sync* sync, long long outer, int lag, int ring_slots, unsigned tiles0, unsigned tiles1,
@@ -886,47 +920,22 @@ int mifft_launch_chain(const mifft_pass* passes, int32_t npasses, void* const bu
     return 0;
 }
 
+int mifft_fused2_kernel(const mifft_pass* p0, const mifft_pass* p1, uint32_t* tiles0, uint32_t* tiles1) {
+    mifft_fused2_choice c;
+    const int rc = select_fused2(p0, p1, &c);
+    if (rc) return rc;
+    if (tiles0) *tiles0 = c.tiles0;
+    if (tiles1) *tiles1 = c.tiles1;
+    return c.form;
+}
+
 int mifft_launch_fused2(const mifft_pass* p0, const mifft_pass* p1, const void* in0, const void* in1, void* out0, void* out1,
                         void* ring0, void* ring1, int32_t ring_slots, int32_t lag, const mifft_fused_sync* sync, int32_t grid,
                         mifft_stream_t stream) {
-    int rc = validate(p0);
+    mifft_fused2_choice c;
+    int rc = select_fused2(p0, p1, &c);
     if (rc) return rc;
-    rc = validate(p1);
-    if (rc) return rc;
-    if (p0->precision != p1->precision) return set_err(MIFFT_E_INVALID, "fused2: passes of two precisions");
-    const bool f64 = p0->precision == MIFFT_F64;
-    // 2-D form: the ROW pass (x axis, length nx) and the strided COL pass (y axis, length ny) of a 2-D plan, run as two
-    // transposing column passes; fp32: nx, ny in {512, 1024, 2048} (split planes: squares only), fp64: 1024 x 1024
-    const bool twod = p0->kind == MIFFT_PASS_ROW;
-    // split-complex fp32 2-D: the row-first kernel (fft_fused2r.hpp), (ny, nx) in {256, 512, 1024}^2 -- the chain's own order, ROW x from
-    // the planes, COL y to the planes, on the persistent list
-    const bool rowfirst = twod && !f64 && p0->layout == MIFFT_SPLIT && g_debug[MIFFT_DEBUG_NARROW_TILES] != 1 && !g_debug[MIFFT_DEBUG_NO_ROWFIRST] &&
-                          mifft_fused2r_f32(p1->L, p0->L, nullptr, 0, nullptr, 1) == 0;
-    if (twod) {
-        auto side = [](int L) { return L == 512 || L == 1024 || L == 2048; };
-        auto side64 = [](int L) { return L == 512 || L == 1024; };
-        // a 256-point axis (interleaved): fp32 on the 32-column tiles next to a side <= 1024, fp64 next to a side <= 512
-        const bool small = p0->layout != MIFFT_SPLIT && (p0->L == 256 || p1->L == 256) &&
-                           (f64 ? (p0->L <= 512 && p1->L <= 512 && p0->L >= 256 && p1->L >= 256)
-                                : (g_debug[MIFFT_DEBUG_NARROW_TILES] != 1 && mifft_fused2dw_f32(p1->L, p0->L, nullptr, 0, nullptr, 1, nullptr, nullptr) == 0));
-        const bool okL = small || rowfirst || (f64 ? (side64(p0->L) && side64(p1->L) && ((p0->L == 1024 && p1->L == 1024) || p0->layout != MIFFT_SPLIT))
-                             : (side(p0->L) && side(p1->L) && (p0->L == p1->L || p0->layout != MIFFT_SPLIT)));
-        if (p1->kind != MIFFT_PASS_COL || !okL || p1->S != p0->L || p1->M != 1 ||
-            p0->outer != p1->outer * p1->L || p0->layout != p1->layout || p0->inverse != p1->inverse)
-            return set_err(MIFFT_E_UNSUPPORTED, "fused2: the 2-D form takes (ny, nx) in {512, 1024, 2048}^2 (fp32; interleaved: also a 256-point side next to one <= 1024; split planes: {256, 512, 1024}^2 and the 2048 square) / {256, 512, 1024}^2 (fp64; split planes: 1024 x 1024; 256 only next to <= 512)");
-    } else {
-    if (p0->kind != MIFFT_PASS_COL || p1->kind != MIFFT_PASS_COL || p0->S != 1 || p0->M != p1->L || p1->M != 1 ||
-        p1->S != p0->L || p0->outer != p1->outer || p0->layout != p1->layout || p0->inverse != p1->inverse)
-        return set_err(MIFFT_E_INVALID, "fused2: passes are not the two passes of one long contiguous axis");
-    auto ok_len = [](int L) { return L == 256 || L == 512 || L == 1024; };
-    const bool big = p0->L == 2048 && (p1->L == 2048 || p1->L == 1024);   // 512-thread tiles (fft_col3.hpp)
-    const bool wide64 = f64 && p0->L == 2048 && (p1->L == 2048 || p1->L == 1024) && p0->layout == MIFFT_INTERLEAVED;   // fft_fusedx_f64.hip
-    const bool small64 = f64 && (p0->L == 256 || p0->L == 512) && (p1->L == 256 || p1->L == 512) && p0->L >= p1->L;
-    const bool mid64 = f64 && p0->L == 1024 && (p1->L == 1024 || p1->L == 512);
-    if (f64 ? (!wide64 && !small64 && !mid64) : (!big && (!ok_len(p0->L) || !ok_len(p1->L)))) return set_err(MIFFT_E_UNSUPPORTED, "fused2: no kernel for %d x %d", p0->L, p1->L);
-    }
-    const bool wide64 = !twod && f64 && p0->L == 2048;
-    const bool split = p0->layout == MIFFT_SPLIT;
+    const bool f64 = p0->precision == MIFFT_F64, split = p0->layout == MIFFT_SPLIT;
     if (!in0 || !out0 || !ring0 || (split && (!in1 || !out1))) return set_err(MIFFT_E_INVALID, "fused2: null buffer");
     (void)ring1;  // the ring is always interleaved
     if (grid < 1) return set_err(MIFFT_E_INVALID, "fused2: grid >= 1");
@@ -940,57 +949,40 @@ int mifft_launch_fused2(const mifft_pass* p0, const mifft_pass* p1, const void* 
     fill_args(p1, ring0, nullptr, out0, out1, &f.p1);
     f.p0.ostride_out = n;  // ring slot pitch
     f.p1.ostride_in = n;
-    if (rowfirst) {
-        f.p0.nt = 4;                // the ring is written through (the consumers acquire it, fft_fused2.hpp)
-        f.p0.scale = p0->scale;
-        f.p1.logMS = f.p1.logS = ilog2(p0->L);   // M = 1, S = nx
-        f.p1.has_tw = 0;
-    } else if (twod) {
-        // pass 0 = the y axis as a transposing column pass over in[y][x] (ny rows of M = nx columns, S = 1) -> ring[x][ky], with the
-        // COL pass's table w(ny); pass 1 = the x axis as the same pass over ring[x][ky] (nx rows of ny columns) -> out[ky][kx],
-        // with the ROW pass's table w(nx)
-        f.p0.tw_L = p1->tw_L;
-        f.p1.tw_L = p0->tw_L;
-        f.p0.ostride_in = p1->outer_stride_in;
-        f.p0.logMS = ilog2(p0->L); f.p0.logS = 0; f.p0.has_tw = 0; f.p0.total = p1->outer * p0->L;
-        f.p1.logMS = ilog2(p1->L); f.p1.logS = 0; f.p1.has_tw = 0; f.p1.total = p1->outer * p1->L;
+    const bool twod = p0->kind == MIFFT_PASS_ROW;
+    const int a = twod ? p1->L : p0->L, b = twod ? p0->L : p1->L;            // what the units are keyed on: (L0, L1) / (ny, nx)
+    mifft_fused2_unit* unit = f64 ? mifft_fused3_f64 : mifft_fused2_f32;      // the 1-D launcher of the precision, on the descriptors as they are
+    switch (c.form) {
+        case MIFFT_FUSED2_KERNEL_2D_ROWFIRST:
+            unit = mifft_fused2r_f32;
+            f.p0.nt = 4;                // the ring is written through (the consumers acquire it, fft_fused2.hpp)
+            f.p0.scale = p0->scale;
+            f.p1.logMS = f.p1.logS = ilog2(p0->L);   // M = 1, S = nx
+            f.p1.has_tw = 0;
+            break;
+        case MIFFT_FUSED2_KERNEL_2D:
+        case MIFFT_FUSED2_KERNEL_2D_WIDE:
+        case MIFFT_FUSED2_KERNEL_2D_BIG:
+            unit = c.form == MIFFT_FUSED2_KERNEL_2D_WIDE ? mifft_fused2dw_f32 : f64 ? mifft_fused3d_f64 : mifft_fused2d_f32;
+            // pass 0 = the y axis as a transposing column pass over in[y][x] (ny rows of M = nx columns, S = 1) -> ring[x][ky], with the
+            // COL pass's table w(ny); pass 1 = the x axis as the same pass over ring[x][ky] (nx rows of ny columns) -> out[ky][kx],
+            // with the ROW pass's table w(nx)
+            f.p0.tw_L = p1->tw_L;
+            f.p1.tw_L = p0->tw_L;
+            f.p0.ostride_in = p1->outer_stride_in;
+            f.p0.logMS = ilog2(p0->L); f.p0.logS = 0; f.p0.has_tw = 0; f.p0.total = p1->outer * p0->L;
+            f.p1.logMS = ilog2(p1->L); f.p1.logS = 0; f.p1.has_tw = 0; f.p1.total = p1->outer * p1->L;
+            break;
+        case MIFFT_FUSED2_KERNEL_1D_WIDE:
+        case MIFFT_FUSED2_KERNEL_1D_MIXED: unit = mifft_fused2w_f32; break;
+        case MIFFT_FUSED2_KERNEL_1D_CHAIN64: unit = mifft_fusedx_f64; break;
+        default: break;
     }
-    // tiles per transform: 2-D: nx / 16 column tiles in pass 0, ny / 16 in pass 1; 1-D: L1 / 16 and L0 / 16 (fp64 2048-point
-    // passes: the tile widths of fft_fusedx_f64.hip)
-    unsigned tiles0 = twod ? (unsigned)(p0->L / 16) : (unsigned)(p0->M / 16), tiles1 = twod ? (unsigned)(p1->L / 16) : (unsigned)(p1->S / 16);
-    if (rowfirst) {                 // groups of 16 rows, then tiles of 16 columns
-        tiles0 = (unsigned)(p1->L / 16);
-        tiles1 = (unsigned)(p0->L / 16);
-    }
-    if (wide64 && mifft_fusedx_f64(p0->L, p1->L, nullptr, 0, nullptr, 1, &tiles0, &tiles1) != 0)
-        return set_err(MIFFT_E_UNSUPPORTED, "fused2: no kernel for %d x %d", p0->L, p1->L);
-    // fp32 interleaved 2^16 ... 2^18: 32-column tiles (fft_col2w.hpp) -- half as many tiles per pass
-    const bool narrow = g_debug[MIFFT_DEBUG_NARROW_TILES] == 1;
-    const bool mixed32 = !twod && !f64 && !split && p0->L == 1024 && p1->L == 512 && !narrow;        // 2^19: the second pass only
-    const bool wide32 = mixed32 || (!twod && !f64 && !split && p0->L <= 512 && p1->L <= 512 && p0->L >= p1->L && !narrow);
-    if (wide32) {
-        if (!mixed32) tiles0 /= 2;
-        tiles1 /= 2;
-    }
-    // split-complex fp32 on the 256-thread tiles (1-D: L0, L1 <= 1024; 2-D: the 512 and 1024 squares): an item is the two sibling
-    // 16-column tiles side by side in one 512-thread work-group (fft_fused2s_kernel)
-    const bool siblings = !f64 && split && !narrow && !rowfirst && p0->L <= 1024 && p1->L <= 1024;
-    if (siblings) {
-        tiles0 /= 2;
-        tiles1 /= 2;
-    }
-    // 2-D fp32 interleaved with a 512-point axis: that axis' pass on 32-column tiles (p1->L = ny, p0->L = nx)
-    const bool wide2d = twod && !f64 && !split && !narrow && mifft_fused2dw_f32(p1->L, p0->L, nullptr, 0, nullptr, 1, &tiles0, &tiles1) == 0;
-    rc = fill_ctl(&f.c, sync, p1->outer, lag, ring_slots, tiles0, tiles1, (hipStream_t)stream, "fused2");
+    rc = fill_ctl(&f.c, sync, p1->outer, lag, ring_slots, c.tiles0, c.tiles1, (hipStream_t)stream, "fused2");
     if (rc) return rc;
-    rc = rowfirst ? mifft_fused2r_f32(p1->L, p0->L, &f, (unsigned)grid, (hipStream_t)stream, 0) :
-         wide2d ? mifft_fused2dw_f32(p1->L, p0->L, &f, (unsigned)grid, (hipStream_t)stream, 0, nullptr, nullptr) :
-         wide32 ? mifft_fused2w_f32_launch(p0->L, p1->L, &f, (unsigned)grid, (hipStream_t)stream) :
-         wide64 ? mifft_fusedx_f64(p0->L, p1->L, &f, (unsigned)grid, (hipStream_t)stream, 0, nullptr, nullptr) : twod ? (f64 ? mifft_fused3d_f64_launch(p1->L, p0->L, &f, split ? 1 : 0, (unsigned)grid, (hipStream_t)stream)
-                     : mifft_fused2d_f32_launch(p1->L, p0->L, &f, split ? 1 : 0, (unsigned)grid, (hipStream_t)stream))
-       : f64 ? mifft_fused3_f64_launch(p0->L, p1->L, &f, split ? 1 : 0, (unsigned)grid, (hipStream_t)stream)
-             : mifft_fused2_f32_launch(p0->L, p1->L, &f, split ? 1 : 0, (unsigned)grid, (hipStream_t)stream);
-    if (rc == MIFFT_E_UNSUPPORTED) return set_err(rc, "fused2: no kernel for %d x %d", p0->L, p1->L);
+    rc = unit(a, b, split ? 1 : 0, &f, (unsigned)grid, (hipStream_t)stream, 0, &c);
+    // (the unit answered the selector under the same switches a moment ago; should it refuse now, that is still no HIP error)
+    if (rc == MIFFT_E_UNSUPPORTED || rc == 1) return set_err(MIFFT_E_UNSUPPORTED, "fused2: no kernel for %d x %d", p0->L, p1->L);
     return hip_check((hipError_t)rc, "kernel launch");
 }
 

@@ -516,6 +516,7 @@ REGISTRY = {
         "test_split_plane_strategies": lambda p: [_c((p["n"],), F32, p["batch"], p["strat"]), _c((p["n"],), F32, p["batch"], "chain")],
         "test_golden_fixture_through_hip": lambda p: [_c(p["entry"]["shape"], numpy.dtype(p["entry"]["dtype"]).type, p["entry"]["batch"])],
         "test_reference_error_grid": lambda p: [_c(p["shape"], p["dtype"], p["batch"])],
+        "test_fused2_refuses_a_shape_without_a_kernel_before_it_touches_the_counters": None,      # (a refusal: no kernel runs)
     },
     "test_full_size_gpu": {
         "test_config2_full": lambda p: [_c((1 << 20,), C64, 4096)],

@@ -456,3 +456,32 @@ def test_reference_error_grid(ctx, shape, dtype, batch):
     assertions of testErrors (test/test_errors.py:18-114) with its thresholds, plus the north star's max-norm bound."""
     x, y, z = getDimensions(shape)
     run_protocol(ctx, shape, dtype, batch, seed=4321, check_oracle=(x * y * z * batch <= (1 << 16)))
+
+
+def test_fused2_refuses_a_shape_without_a_kernel_before_it_touches_the_counters(ctx):
+    """mifft_launch_fused2 for fp32 interleaved 1-D 256 x 512 -- lengths of the form, in an order no instance has: MIFFT_E_UNSUPPORTED
+    with "no kernel for 256 x 512" from the selector, before the sync block is looked at, so the single-set form's counters are not
+    zeroed (they were, until the selection moved in front of the work-list set-up).  No kernel runs."""
+    import ctypes
+    from pyfft_amd import _native as N
+    hip = ctx.hip
+    L0, L1, outer = 256, 512, 4
+    s = hip.Stream()
+    data, out, ring = (hip.DeviceArray((L0 * L1 * outer,), numpy.complex64) for _ in range(3))
+    tables = hip.DeviceArray((L0 * L1,), numpy.complex64)       # (never read; real memory all the same)
+    counters = hip.DeviceArray((N.fused2_counter_bytes(outer),), numpy.uint8)
+    N.check(N.lib.mifft_memset(counters.ptr, 0xA5, counters.nbytes, s.handle))
+    s.synchronize()
+    d = (N.MifftPass * 2)()
+    for p in d:
+        p.kind, p.precision, p.layout, p.outer, p.scale, p.tw_shift = N.PASS_COL, N.F32, N.INTERLEAVED, outer, 1.0, 10
+        p.outer_stride_in = p.outer_stride_out = L0 * L1
+        p.tw_L = p.tw_lo = p.tw_hi = tables.ptr
+    d[0].L, d[0].M, d[0].S = L0, L1, 1
+    d[1].L, d[1].M, d[1].S = L1, 1, L0
+    sync = N.MifftFusedSync(counters.ptr, None, None)
+    rc = N.lib.mifft_launch_fused2(ctypes.byref(d[0]), ctypes.byref(d[1]), data.ptr, None, out.ptr, None, ring.ptr, None, 2, 1,
+                                   ctypes.byref(sync), 8, s.handle)
+    assert rc == N.E_UNSUPPORTED and "no kernel for 256 x 512" in N.last_error(), (rc, N.last_error())
+    s.synchronize()
+    assert (counters.get() == 0xA5).all()

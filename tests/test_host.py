@@ -862,6 +862,105 @@ def test_nd_kernel_snapshot():
     assert count["nd"] > 100000 and count["refused"] > 100000 and sum(seen.values()) + count["nd"] + count["refused"] == 1404000
 
 
+# MIFFT_FUSED2_KERNEL_* 1 ... 10, in the order of make_fused2_kernel_snapshot.FORMS
+FUSED2_FORMS = ("1D", "1D_SIBLINGS", "1D_WIDE", "1D_MIXED", "2D", "2D_WIDE", "1D_BIG", "2D_BIG", "2D_ROWFIRST", "1D_CHAIN64")
+
+
+def test_fused2_kernel_snapshot():
+    """mifft_fused2_kernel -- the one selector mifft_launch_fused2 goes through -- answers what the library launched, and refused, before
+    the selection was written in one place: tests/golden/fused2_kernel_snapshot.json holds the form and the tiles per transform, or the
+    refusal code, of every point of the grid (written from the earlier code, see make_fused2_kernel_snapshot.py) under the default
+    switches and under each setting of the four switches a persistent launch reads."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    import make_fused2_kernel_snapshot as snap
+    from pyfft_amd import _native as N
+    want = snap.load()
+    assert want["forms"] == list(snap.FORMS) and want["settings"] == [list(s) for s in snap.SETTINGS]
+    assert [getattr(N, "FUSED2_KERNEL_" + n) for n in FUSED2_FORMS] == list(range(1, len(snap.FORMS) + 1))
+    got, bad = snap.enumerate_library()
+    assert got == want["points"], sorted(k for k in set(got) | set(want["points"]) if got.get(k) != want["points"].get(k))[:10]
+    assert bad == want["malformed"]
+    # the file as the generator writes it, byte for byte
+    import tempfile
+    with tempfile.TemporaryDirectory() as tmp:
+        snap.dump(got, bad, os.path.join(tmp, "again.json"))
+        assert open(os.path.join(tmp, "again.json"), "rb").read() == open(snap.PATH, "rb").read()
+    # not vacuous: 10 settings x 2 precisions x 2 layouts x (1-D, 2-D) x 36 pairs; every form occurs; both refusal codes occur (every
+    # pair of the grid is well formed, so MIFFT_E_INVALID comes from the malformed pairs)
+    points = want["points"]
+    assert len(points) == 80 and all(len(g) == 36 for g in points.values())
+    assert set(p[2] for g in points.values() for p in g if len(p) == 5) == set(snap.FORMS)
+    assert set(p[2] for g in points.values() for p in g if len(p) == 3) == {N.E_UNSUPPORTED}
+    assert set(b[1] for b in want["malformed"]) == {N.E_UNSUPPORTED, N.E_INVALID}
+    # every setting the SELECTION reads changes at least one point against the default; the three that act inside the chosen kernel
+    # (non-temporal stores; the paired-lane forms 0 and 3 of the 1024 x 1024 kernel, both instances of one template) change none
+    for name, _, _ in snap.SETTINGS[1:]:
+        changed = [k for k in points if k.startswith(name + "/") and points[k] != points["default/" + k.split("/", 1)[1]]]
+        assert bool(changed) == (name not in snap.SAME_AS_DEFAULT), (name, changed)
+
+
+def test_persistent_rules_name_kernels_the_library_has(monkeypatch):
+    """Every fused2 rule of pyfft_amd/tuning_gfx950.json that a plan of make_strategy_snapshot.py's shapes matches, under each of its
+    switch settings, names a kernel the library runs (mifft_fused2_kernel on the plan's own two descriptors answers a form), on the
+    first-pass tile width the rule states: the planner's tiles per transform are the work list's.  KNOWN: the rules that already named
+    no kernel when this test was written -- refused with MIFFT_E_UNSUPPORTED, exactly where listed."""
+    import ctypes
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    import make_strategy_snapshot as snap
+    from pyfft_amd import _debug as D
+    from pyfft_amd import _native as N
+    from pyfft_amd.machine import Machine
+    from pyfft_amd.plan import FFTPlan
+    # rule name -> which of its plans the library refuses: (narrow tiles, shape class) -> bool.  The split-plane squares ran two
+    # transposing passes on sibling tiles until the row-first kernel replaced those instances (what is left of them is on request, and
+    # matched only where a switch takes the row-first rule away; the 2048 square always); MIFFT_DEBUG_NARROW_TILES = 1 asks for the
+    # rounds 1-3 forms, which the fp32 1-D launcher refuses and the interleaved 512 square no longer has
+    KNOWN = {
+        "fp32 planes squares as two transposing passes on sibling tiles": lambda narrow, cls: True,
+        "fp32 planes 1024 square as two transposing passes on sibling tiles": lambda narrow, cls: True,
+        "fp32 planes squares, 16-column tiles (rounds 1-3 forms)": lambda narrow, cls: True,
+        "fp32 planes 2048 square": lambda narrow, cls: True,
+        "fp32 1-D on 16-column tiles (BASELINE config 2: 1024 x 1024)": lambda narrow, cls: narrow,
+        "fp32 2-D {512, 1024}^2 on 16-column tiles (BASELINE config 3)": lambda narrow, cls: narrow and cls["ny"] == cls["nx"] == 512,
+    }
+    mach = Machine(*snap.MACHINES["full"])
+    agreed, refused, wrong = 0, set(), []
+    try:
+        for sname, env, narrow in snap.SWITCHES:
+            for k in snap.ENV_KEYS:
+                monkeypatch.delenv(k, raising=False)
+            for k, v in env.items():
+                monkeypatch.setenv(k, v)
+            N.lib.mifft_debug_set(N.DEBUG_NARROW_TILES, narrow)
+            for shape in snap.shapes():
+                for dt in snap.DTYPES:
+                    plan = FFTPlan(_FakeContext(mach), shape, dtype=numpy.dtype(dt))
+                    rule = plan._persistent_rule()       # (forwards PYFFT_AMD_NO_SPLIT_ROWFIRST to the thread's native switch)
+                    if rule is None or rule["strategy"] != "fused2":
+                        continue
+                    cls = plan._shape_class()
+                    d = plan._descriptors(4, False, False)
+                    tiles0 = ctypes.c_uint32(0)
+                    form = N.lib.mifft_fused2_kernel(ctypes.byref(d[0]), ctypes.byref(d[1]), ctypes.byref(tiles0), None)
+                    if KNOWN.get(rule["name"], lambda narrow, cls: False)(bool(narrow), cls):
+                        refused.add(rule["name"])
+                        ok = form == N.E_UNSUPPORTED
+                    else:
+                        agreed += 1
+                        ok = 1 <= form <= len(FUSED2_FORMS) and tiles0.value == int(cls[rule["extent0"]]) // int(rule["cols0"])
+                    if not ok:
+                        wrong.append((sname, shape, dt, rule["name"], form, tiles0.value, N.last_error()))
+    finally:
+        N.lib.mifft_debug_set(N.DEBUG_NARROW_TILES, 0)
+        for k in snap.ENV_KEYS:
+            monkeypatch.delenv(k, raising=False)
+        D.no_split_rowfirst()
+    assert not wrong, wrong[:10]
+    assert refused == set(KNOWN) and agreed > 300
+
+
 def test_row_supported_snapshot():
     """The row families (complex, complex32, real, convolution, cosine / sine) take their work-group shapes from one table
     (csrc/fft_row_shapes.hpp) and name their lengths in per-family lists.  Which lengths each has a kernel for is what the library
