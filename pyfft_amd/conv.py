@@ -21,13 +21,9 @@ Forms (plan.conv_form):
 import numpy
 
 from . import _native as N
-from .generic import _SubContext
+from .extplan import ExtPlan, buffer_nbytes, pow2_shape
 from .plan import FFTPlan, on_plan_device, _twiddle_table
-from .real import RealFFTPlan, real_params, spectrum_shape, _buffer_nbytes
-
-
-def _is_pow2(n):
-    return n >= 1 and (n & (n - 1)) == 0
+from .real import RealFFTPlan, real_params, spectrum_shape
 
 
 def conv_params(shape, dtype, real):
@@ -38,16 +34,7 @@ def conv_params(shape, dtype, real):
         except ValueError as e:
             raise ValueError("pyfft_amd: convolve=True: %s" % e)
         return shape, prec, rdt, cdt
-    if isinstance(shape, (int, numpy.integer)) and not isinstance(shape, bool):
-        shape = (shape,)
-    if not isinstance(shape, tuple) or not 1 <= len(shape) <= 3:
-        raise ValueError("pyfft_amd: convolve=True: wrong shape")
-    for v in shape:
-        if not isinstance(v, (int, numpy.integer)) or isinstance(v, bool) or v < 1:
-            raise ValueError("pyfft_amd: convolve=True: wrong shape")
-    shape = tuple(int(v) for v in shape)
-    if not all(_is_pow2(v) for v in shape):
-        raise ValueError("pyfft_amd: convolve=True: array dimensions must be powers of two")
+    shape = pow2_shape(shape, "pyfft_amd: convolve=True: wrong shape", "pyfft_amd: convolve=True: array dimensions must be powers of two")
     if isinstance(dtype, str) and dtype.lower() in ("complex32", "chalf"):
         raise ValueError("pyfft_amd: convolve=True has no complex32 form")
     if "complex32" in str(dtype):
@@ -65,7 +52,7 @@ def conv_params(shape, dtype, real):
     raise ValueError("pyfft_amd: convolve=True: data type " + str(dtype) + " is not supported")
 
 
-class ConvPlan(object):
+class ConvPlan(ExtPlan):
     """Convolution plan: see the module docstring."""
 
     @staticmethod
@@ -75,25 +62,17 @@ class ConvPlan(object):
     def __init__(self, context, shape, dtype=numpy.complex64, normalize=True, wait_for_finish=None, fast_math=True, scale=1.0, real=False):
         self._real = bool(real)
         self._shape, self._precision, self._dtype, self._cdtype = conv_params(shape, dtype, self._real)
-        self._context = context
+        ExtPlan.__init__(self, context, wait_for_finish)
         self._normalize = bool(normalize)
         self._scale = float(scale)
-        self._wait_for_finish = wait_for_finish
         self._size = int(numpy.prod(self._shape))
         self._spec_points = int(numpy.prod(spectrum_shape(self._shape))) if self._real else self._size
         n = self._shape[0]
         fused = len(self._shape) == 1 and N.lib.mifft_conv_row_supported(self._precision, 1 if self._real else 0, n) == 0
         self.conv_form = "fused_row" if fused else "composed"
-        self._sub = _SubContext(context)
-        self._scratch = None
-        self._last_batch = 0
-        self._captured = False
-        self._capture_keepalive = []
         on_plan_device(ConvPlan._build)(self)
 
     def _build(self):
-        ctx = self._context
-        self._inner = None
         self._tw = self._tw_sep = None
         # the plain plan of the shape: the composed form's two transforms and filter_spectrum's forward (scale 1, no normalisation)
         shp = self._shape if len(self._shape) > 1 else self._shape[0]
@@ -104,13 +83,9 @@ class ConvPlan(object):
         if self.conv_form == "fused_row":
             n = self._shape[0]
             L = n // 2 if self._real else n
-            host = numpy.ascontiguousarray(_twiddle_table(L, L, 1, self._cdtype))
-            self._tw = ctx.allocate_raw(host.nbytes)
-            ctx.upload(self._tw, host)
+            self._tw = self._upload(_twiddle_table(L, L, 1, self._cdtype))
             if self._real:
-                host = numpy.ascontiguousarray(_twiddle_table(n, L + 1, 1, self._cdtype))
-                self._tw_sep = ctx.allocate_raw(host.nbytes)
-                ctx.upload(self._tw_sep, host)
+                self._tw_sep = self._upload(_twiddle_table(n, L + 1, 1, self._cdtype))
 
     @property
     def kernel(self):
@@ -123,31 +98,13 @@ class ConvPlan(object):
     def _prepare(self, batch):
         """Real composed form: plan-owned half-spectrum scratch, sized by batch (kept alive for a graph that recorded the previous one)."""
         need = self._real and self.conv_form == "composed"
-        if batch == self._last_batch and (self._scratch is not None or not need):
-            return
-        if need and self._context.capturing():
-            raise RuntimeError("pyfft_amd: execute() on a capturing stream needs one eager execute() of the same batch first")
-        self._release_scratch()
-        if need:
-            self._scratch = self._context.allocate(batch * self._spec_points * self._cdtype.itemsize)
-        self._last_batch = batch         # (committed only now: after a failed allocation the plan is as close() leaves it)
-
-    def _release_scratch(self):
-        """Let go of the scratch: to the keep-alive list once a graph has recorded an execute (it replays on it); else, where it came
-        from a mempool, only after the plan's own asynchronous executes have finished with it (hipFree does that waiting itself)."""
-        if self._scratch is not None:
-            if self._captured:
-                self._capture_keepalive.append(self._scratch)
-            else:
-                self._context.wait_scratch()
-        self._scratch = None
-        self._last_batch = 0
+        self._size_scratch(batch, batch * self._spec_points * self._cdtype.itemsize if need else None)
 
     def _check_buffers(self, batch, x, y, spectrum, spectrum_batch):
         data_bytes = batch * self._size * self._dtype.itemsize
         spec_bytes = spectrum_batch * self._spec_points * self._cdtype.itemsize
         for what, obj, need in (("input", x, data_bytes), ("output", y, data_bytes), ("spectrum", spectrum, spec_bytes)):
-            nb = _buffer_nbytes(obj)
+            nb = buffer_nbytes(obj)
             if nb is not None and nb < need:
                 raise ValueError("pyfft_amd: convolve plan %s buffer holds %d bytes, batch %d needs %d" % (what, nb, batch, need))
         ptr = self._context.pointer_of
@@ -175,18 +132,9 @@ class ConvPlan(object):
     def _execute(self, wait_for_finish, batch, x, y, spectrum, spectrum_batch, correlate):
         ctx = self._context
         xs, ys, ss = self._check_buffers(batch, x, y, spectrum, spectrum_batch)
-        ctx.createQueue((x, y, spectrum))
-        wait = self._wait_for_finish if wait_for_finish is None else wait_for_finish
-        capturing = ctx.capturing()
-        if capturing and wait:
-            raise RuntimeError("pyfft_amd: execute() on a capturing stream cannot wait for the result: build the plan with stream= "
-                               "(or wait_for_finish=False), or pass wait_for_finish=False to this call")
+        wait, capturing = self._open((x, y, spectrum), wait_for_finish)
         self._prepare(batch)
-        ctx.order_scratch(capturing)
-        if capturing:
-            from .hip import Graph
-            self._captured = True
-            Graph.retain(self)
+        self._stream_step(capturing)
         factor = self._scale / (self._size if self._normalize else 1.0)
         pitch = self._spec_points if spectrum_batch > 1 else 0
         cj = 1 if correlate else 0
@@ -209,11 +157,7 @@ class ConvPlan(object):
             N.check(N.lib.mifft_aux_mul_spectrum(self._precision, ys, ss, batch, self._size, pitch, cj, factor, ctx.stream_handle()),
                     "mifft_aux_mul_spectrum")
             self._inner.execute(ys, inverse=True, batch=batch, wait_for_finish=False)
-        if wait:
-            self.finish()
-            return None
-        ctx.flush()
-        return ctx.getQueue()
+        return self._epilogue(wait)
 
     def execute(self, x, y=None, spectrum=None, batch=1, correlate=False, spectrum_batch=1, wait_for_finish=None):
         """y = scale * IFFTN(FFTN(x) * S) for `batch` items; y None: in place.  S = spectrum (conj(spectrum) with correlate=True),
@@ -236,51 +180,16 @@ class ConvPlan(object):
         batch = int(batch)
         if batch < 1:
             raise ValueError("batch must be positive")
-        nb = _buffer_nbytes(out)
+        nb = buffer_nbytes(out)
         need = batch * self._spec_points * self._cdtype.itemsize
         if nb is not None and nb < need:
             raise ValueError("pyfft_amd: convolve plan filter_spectrum output holds %d bytes, batch %d needs %d" % (nb, batch, need))
-        ctx = self._context
-        ctx.createQueue((h, out))
-        capturing = ctx.capturing()
-        if capturing and self._wait_for_finish:
-            raise RuntimeError("pyfft_amd: filter_spectrum() on a capturing stream cannot wait for the result: build the plan with stream=")
-        ctx.order_scratch(capturing)
-        if capturing:
-            from .hip import Graph
-            self._captured = True
-            Graph.retain(self)
+        wait, capturing = self._open((h, out), call="filter_spectrum")
+        self._stream_step(capturing)
         self._inner.execute(h, out, batch=batch, wait_for_finish=False)
-        if self._wait_for_finish:
+        if wait:
             self.finish()
         return out
-
-    # ------------------------------------------------------------------------------------
-    @on_plan_device
-    def finish(self):
-        self._context.wait()
-        self._inner.finish()
-
-    @on_plan_device
-    def check(self):
-        self._inner.check()
-
-    def close(self):
-        try:
-            self.finish()
-        finally:
-            self._release_scratch()
-            self._inner.close()
-
-    def release_captured(self):
-        self.finish()
-        self._capture_keepalive = []
-        self._captured = False
-        self._inner.release_captured()
-
-    @property
-    def inner_plan(self):
-        return self._inner
 
     def spectrum_shape(self):
         return spectrum_shape(self._shape) if self._real else tuple(self._shape)

@@ -19,9 +19,9 @@ design is taken as it is: if its impulse response is longer than m taps, the tim
 import numpy
 
 from . import _native as N
-from .generic import _SubContext
+from .extplan import ExtPlan, buffer_nbytes
 from .plan import FFTPlan, on_plan_device, _twiddle_table
-from .real import RealFFTPlan, _buffer_nbytes
+from .real import RealFFTPlan
 
 
 def supported_lengths(precision, real):
@@ -69,7 +69,7 @@ def fir_params(shape, dtype, real, taps):
     return n, prec, ddt, cdt, m, overlap
 
 
-class FirPlan(object):
+class FirPlan(ExtPlan):
     """Overlap-save FIR plan: see the module docstring."""
 
     fir_form = "fused_row"
@@ -83,20 +83,13 @@ class FirPlan(object):
         self._real = bool(real)
         self._n, self._precision, self._dtype, self._cdtype, self._taps, self.overlap = fir_params(shape, dtype, self._real, taps)
         self.hop = self._n - self.overlap
-        self._context = context
+        ExtPlan.__init__(self, context, wait_for_finish)
         self._normalize = bool(normalize)
         self._scale = float(scale)
-        self._wait_for_finish = wait_for_finish
         self._spec_points = self._n // 2 + 1 if self._real else self._n
-        self._sub = _SubContext(context)
-        self._scratch = None
-        self._last_batch = 0
-        self._captured = False
-        self._capture_keepalive = []
         on_plan_device(FirPlan._build)(self)
 
     def _build(self):
-        ctx = self._context
         n = self._n
         # the plain plan of the block length: filter_spectrum's forward (scale 1, no normalisation)
         if self._real:
@@ -104,14 +97,8 @@ class FirPlan(object):
         else:
             self._inner = FFTPlan(self._sub, n, dtype=self._cdtype, normalize=False, wait_for_finish=False, scale=1.0)
         L = n // 2 if self._real else n
-        host = numpy.ascontiguousarray(_twiddle_table(L, L, 1, self._cdtype))
-        self._tw = ctx.allocate_raw(host.nbytes)
-        ctx.upload(self._tw, host)
-        self._tw_sep = None
-        if self._real:
-            host = numpy.ascontiguousarray(_twiddle_table(n, L + 1, 1, self._cdtype))
-            self._tw_sep = ctx.allocate_raw(host.nbytes)
-            ctx.upload(self._tw_sep, host)
+        self._tw = self._upload(_twiddle_table(L, L, 1, self._cdtype))
+        self._tw_sep = self._upload(_twiddle_table(n, L + 1, 1, self._cdtype)) if self._real else None
 
     @property
     def kernel(self):
@@ -131,33 +118,15 @@ class FirPlan(object):
 
     # ------------------------------------------------------------------------------------
     def _prepare(self, batch):
-        """filter_spectrum's padded taps: plan-owned scratch of n points per filter, sized by batch (kept alive for a graph that
-        recorded the previous one)."""
-        if batch == self._last_batch and self._scratch is not None:
-            return
-        if self._context.capturing():
-            raise RuntimeError("pyfft_amd: filter_spectrum() on a capturing stream needs one eager filter_spectrum() of the same batch first")
-        self._release_scratch()
-        self._scratch = self._context.allocate(batch * self._n * self._dtype.itemsize)
-        self._last_batch = batch         # (committed only now: after a failed allocation the plan is as close() leaves it)
-
-    def _release_scratch(self):
-        """Let go of the scratch: to the keep-alive list once a graph has recorded a launch on it; else, where it came from a mempool,
-        only after the plan's own asynchronous launches have finished with it (hipFree does that waiting itself)."""
-        if self._scratch is not None:
-            if self._captured:
-                self._capture_keepalive.append(self._scratch)
-            else:
-                self._context.wait_scratch()
-        self._scratch = None
-        self._last_batch = 0
+        """filter_spectrum's padded taps: scratch of n points per filter (execute needs none and never prepares)."""
+        self._size_scratch(batch, batch * self._n * self._dtype.itemsize, call="filter_spectrum")
 
     def _check_buffers(self, batch, x, y, spectrum, spectrum_batch, length, pitch):
         isz, cs = self._dtype.itemsize, self._cdtype.itemsize
         data_bytes = ((batch - 1) * pitch + length) * isz
         spec_bytes = spectrum_batch * self._spec_points * cs
         for what, obj, need in (("input", x, data_bytes), ("output", y, data_bytes), ("spectrum", spectrum, spec_bytes)):
-            nb = _buffer_nbytes(obj)
+            nb = buffer_nbytes(obj)
             if nb is not None and nb < need:
                 raise ValueError("pyfft_amd: taps= plan %s buffer holds %d bytes, batch %d of length %d needs %d" % (what, nb, batch, length, need))
         ptr = self._context.pointer_of
@@ -176,28 +145,15 @@ class FirPlan(object):
     def _execute(self, wait_for_finish, batch, x, y, spectrum, spectrum_batch, length, pitch):
         ctx = self._context
         xs, ys, ss = self._check_buffers(batch, x, y, spectrum, spectrum_batch, length, pitch)
-        ctx.createQueue((x, y, spectrum))
-        wait = self._wait_for_finish if wait_for_finish is None else wait_for_finish
-        capturing = ctx.capturing()
-        if capturing and wait:
-            raise RuntimeError("pyfft_amd: execute() on a capturing stream cannot wait for the result: build the plan with stream= "
-                               "(or wait_for_finish=False), or pass wait_for_finish=False to this call")
-        ctx.order_scratch(capturing)
-        if capturing:
-            from .hip import Graph
-            self._captured = True
-            Graph.retain(self)
+        wait, capturing = self._open((x, y, spectrum), wait_for_finish)
+        self._stream_step(capturing)
         factor = self._scale / (self._n if self._normalize else 1.0)
         ptr = ctx.pointer_of
         N.check(N.lib.mifft_launch_fir_row(self._precision, 1 if self._real else 0, self._n, self.overlap, length, pitch, batch, xs, ys, ss,
                                            self._spec_points if spectrum_batch > 1 else 0, ptr(self._tw),
                                            ptr(self._tw_sep) if self._tw_sep is not None else None, factor, ctx.stream_handle()),
                 "mifft_launch_fir_row")
-        if wait:
-            self.finish()
-            return None
-        ctx.flush()
-        return ctx.getQueue()
+        return self._epilogue(wait)
 
     def execute(self, x, y=None, spectrum=None, length=None, batch=1, pitch=None, spectrum_batch=1, correlate=False, wait_for_finish=None):
         """y[i, t] = scale * sum_j h[j] x[i, t - j], 0 <= t < length, for `batch` items `pitch` elements apart on both sides (default:
@@ -240,54 +196,20 @@ class FirPlan(object):
             raise ValueError("batch must be positive")
         cs = self._cdtype.itemsize
         for what, obj, need in (("taps", h, batch * self._taps * self._dtype.itemsize), ("output", out, batch * self._spec_points * cs)):
-            nb = _buffer_nbytes(obj)
+            nb = buffer_nbytes(obj)
             if nb is not None and nb < need:
                 raise ValueError("pyfft_amd: taps= plan filter_spectrum %s buffer holds %d bytes, batch %d needs %d" % (what, nb, batch, need))
         ctx = self._context
-        ctx.createQueue((h, out))
-        capturing = ctx.capturing()
-        if capturing and self._wait_for_finish:
-            raise RuntimeError("pyfft_amd: filter_spectrum() on a capturing stream cannot wait for the result: build the plan with stream=")
+        wait, capturing = self._open((h, out), call="filter_spectrum")
         self._prepare(batch)
-        ctx.order_scratch(capturing)
-        if capturing:
-            from .hip import Graph
-            self._captured = True
-            Graph.retain(self)
+        self._stream_step(capturing)
         z = ctx.pointer_of(self._scratch)
         N.check(N.lib.mifft_launch_fir_pad(self._precision, 1 if self._real else 0, self._n, self._taps, batch, ctx.pointer_of(h), z,
                                            ctx.stream_handle()), "mifft_launch_fir_pad")
         self._inner.execute(z, out, batch=batch, wait_for_finish=False)
-        if self._wait_for_finish:
+        if wait:
             self.finish()
         return out
-
-    # ------------------------------------------------------------------------------------
-    @on_plan_device
-    def finish(self):
-        self._context.wait()
-        self._inner.finish()
-
-    @on_plan_device
-    def check(self):
-        self._inner.check()
-
-    def close(self):
-        try:
-            self.finish()
-        finally:
-            self._release_scratch()
-            self._inner.close()
-
-    def release_captured(self):
-        self.finish()
-        self._capture_keepalive = []
-        self._captured = False
-        self._inner.release_captured()
-
-    @property
-    def inner_plan(self):
-        return self._inner
 
     def spectrum_shape(self):
         return (self._spec_points,)

@@ -31,12 +31,9 @@ import numpy
 
 from . import _debug as D
 from . import _native as N
+from .extplan import _SubContext, epilogue, needs_eager_first, stream_step, upload
+from .passes import is_pow2 as _is_pow2          # (the name tests/kernel_coverage.py imports from here)
 from .plan import FFTPlan, normalize_shape, on_plan_device, _twiddle_table
-
-
-def _is_pow2(n):
-    return n >= 1 and (n & (n - 1)) == 0
-
 
 # pi in extended precision (numpy.pi is the float64 one: 1.2e-16 short, which an extended-precision angle would keep)
 _PI_LD = numpy.longdouble("3.14159265358979323846264338327950288")
@@ -110,46 +107,6 @@ def _unit_roots(count, step, period):
 
 class _Axis(object):
     __slots__ = ("n", "m", "plan", "chirp", "bhat", "pow2", "mixed_tw", "blue")
-
-
-class _SubContext(object):
-    """What the inner power-of-two plans see: the outer plan's context with the stream choice frozen (the outer execute()
-    has already picked the stream of this call; an inner plan must not pick another one)."""
-
-    _guard = False      # the outer plan has made its device current before an inner plan runs
-
-    def __init__(self, ctx):
-        self._ctx = ctx
-        self.compute_units = ctx.compute_units
-        self.machine = ctx.machine
-        self.allocate = ctx.allocate
-        self.allocate_raw = ctx.allocate_raw
-        self.upload = ctx.upload
-        self.pointer_of = ctx.pointer_of
-
-    def createQueue(self, buffers=()):
-        pass
-
-    def order_scratch(self, capturing=None):
-        pass            # (the outer execute() has ordered the stream of this call behind the previous one)
-
-    def stream_handle(self):
-        return self._ctx.stream_handle()
-
-    def capturing(self):
-        return self._ctx.capturing()
-
-    def wait(self):
-        self._ctx.wait()
-
-    def wait_scratch(self):
-        self._ctx.wait_scratch()
-
-    def flush(self):
-        pass
-
-    def getQueue(self):
-        return self._ctx.getQueue()
 
 
 class GenericFFTPlan(object):
@@ -316,9 +273,7 @@ class GenericFFTPlan(object):
         return self._rowplans[m]
 
     def _upload(self, host):
-        host = numpy.ascontiguousarray(host)
-        mem = self._context.allocate_raw(host.nbytes)
-        self._context.upload(mem, host)
+        mem = upload(self._context, host)
         self._tables.append(mem)
         return self._context.pointer_of(mem)
 
@@ -358,15 +313,6 @@ class GenericFFTPlan(object):
         hi = roots(((n - 1) >> shift) + 1, 1 << shift, n)
         return (n1, n2, roots(n1, 1, n1), roots(n2, 1, n2), lo, hi, shift)
 
-    def _epilogue(self, wait_for_finish):
-        """The end of every execute (plan.py:250-259): wait (and check for errors) or hand the stream back."""
-        wait = self._wait_for_finish if wait_for_finish is None else wait_for_finish
-        if wait:
-            self.finish()
-            return None
-        self._context.flush()
-        return self._context.getQueue()
-
     def _prepare(self, batch, capturing=False, long_scratch=False):
         """Work arrays of the batch (long_scratch: the scratch of a long smooth transform run in place, allocated by the first
         execute that needs it).  `capturing`: the stream of this call records into a graph, where nothing can be allocated or
@@ -376,7 +322,7 @@ class GenericFFTPlan(object):
         if batch == self._last_batch and (self._work is not None or not needs):
             return
         if capturing and needs:
-            raise RuntimeError("pyfft_amd: execute() on a capturing stream needs one eager execute() of the same batch first")
+            raise RuntimeError(needs_eager_first())
         self._release_work(capturing)
         if needs:
             isz = self._cdtype.itemsize
@@ -412,16 +358,12 @@ class GenericFFTPlan(object):
         ptr = ctx.pointer_of
         ctx.createQueue(ins + outs)
         capturing = ctx.capturing()          # (of the stream of THIS call: createQueue has just chosen it)
+        wait = self._wait_for_finish if wait_for_finish is None else wait_for_finish
         self._prepare(batch, capturing, long_scratch=self._direct_long is not None and ptr(ins[0]) == ptr(outs[0]))
-        ctx.order_scratch(capturing)
-        if capturing:
-            # recorded into a graph (_prepare has refused a batch without work arrays): the graph keeps this plan alive, the plan
-            # keeps the work arrays of the recorded batch
-            from .hip import Graph
-            self._captured = True
-            Graph.retain(self)
+        # (recorded into a graph -- _prepare has refused a batch without work arrays -- the plan keeps the work arrays of the recorded batch)
+        stream_step(self, capturing)
         if self._tiled:
-            return self._execute_tiled(wait_for_finish, bool(inverse), batch, [ptr(b) for b in ins], [ptr(b) for b in outs])
+            return self._execute_tiled(wait, bool(inverse), batch, [ptr(b) for b in ins], [ptr(b) for b in outs])
         if self._direct_nd1:
             inv = bool(inverse)
             factor = self._scale if not inv else 1.0 / ((self._size if self._normalize else 1.0) * self._scale)
@@ -429,7 +371,7 @@ class GenericFFTPlan(object):
             twx, twy, twz = self._direct_nd
             N.check(N.lib.mifft_launch_mixed_nd(self._precision, x, y, z, batch, ptr(ins[0]), ptr(outs[0]), twx, twy, twz, 1 if inv else 0,
                                                 factor, ctx.stream_handle()), "mifft_launch_mixed_nd")
-            return self._epilogue(wait_for_finish)
+            return epilogue(self, wait)
         if self._direct_nd_planes:
             inv = bool(inverse)
             factor = self._scale if not inv else 1.0 / ((self._size if self._normalize else 1.0) * self._scale)
@@ -439,7 +381,7 @@ class GenericFFTPlan(object):
                                                 1.0, ctx.stream_handle()), "mifft_launch_mixed_nd")
             N.check(N.lib.mifft_launch_mixed_lines(self._precision, z, batch, x * y, ptr(outs[0]), ptr(outs[0]), twz, 0, 1 if inv else 0,
                                                    factor, ctx.stream_handle()), "mifft_launch_mixed_lines")
-            return self._epilogue(wait_for_finish)
+            return epilogue(self, wait)
         if self._direct_nd is not None:
             inv = bool(inverse)
             factor = self._scale if not inv else 1.0 / ((self._size if self._normalize else 1.0) * self._scale)
@@ -454,7 +396,7 @@ class GenericFFTPlan(object):
                                                            factor if last else 1.0, ctx.stream_handle()), "mifft_launch_mixed_lines")
                     src = ptr(outs[0])
                 inner *= ax.n
-            return self._epilogue(wait_for_finish)
+            return epilogue(self, wait)
         if self._direct_long is not None:
             n1, n2, tw1, tw2, lo, hi, shift = self._direct_long
             n = n1 * n2
@@ -466,7 +408,7 @@ class GenericFFTPlan(object):
                 mid = ptr(self._work)
             N.check(N.lib.mifft_launch_mixed_long(self._precision, n1, n2, batch, src, mid, dst, tw1, tw2, lo, hi, shift,
                                                   1 if inv else 0, factor, ctx.stream_handle()), "mifft_launch_mixed_long")
-            return self._epilogue(wait_for_finish)
+            return epilogue(self, wait)
         if self._direct_blue:
             n = self._xyz[0]
             m, tw, chirp, bhat = self._axes[0].blue
@@ -474,14 +416,14 @@ class GenericFFTPlan(object):
             factor = self._scale if not inv else 1.0 / ((n if self._normalize else 1.0) * self._scale)
             N.check(N.lib.mifft_launch_bluestein_rows(self._precision, n, m, batch, n, n, ptr(ins[0]), ptr(outs[0]), tw, chirp, bhat,
                                                       1 if inv else 0, factor, ctx.stream_handle()), "mifft_launch_bluestein_rows")
-            return self._epilogue(wait_for_finish)
+            return epilogue(self, wait)
         if self._direct_mixed:
             n = self._xyz[0]
             inv = bool(inverse)
             factor = self._scale if not inv else 1.0 / ((n if self._normalize else 1.0) * self._scale)
             N.check(N.lib.mifft_launch_mixed_rows(self._precision, n, batch, n, n, ptr(ins[0]), ptr(outs[0]), self._axes[0].mixed_tw,
                                                   1 if inv else 0, factor, ctx.stream_handle()), "mifft_launch_mixed_rows")
-            return self._epilogue(wait_for_finish)
+            return epilogue(self, wait)
         nt = batch * self._ntiles
         work, rows = ptr(self._work), ptr(self._rows)
         in0, in1 = ptr(ins[0]), (ptr(ins[1]) if self._split else None)
@@ -544,9 +486,9 @@ class GenericFFTPlan(object):
             factor = 1.0 / ((self._size if self._normalize else 1.0) * self._scale)
         self._copy(dims, dense, user, work, None, out0, out1, conj_out=inverse, scale=factor, dst_split=self._split)
 
-        return self._epilogue(wait_for_finish)
+        return epilogue(self, wait)
 
-    def _execute_tiled(self, wait_for_finish, inverse, batch, src, dst):
+    def _execute_tiled(self, wait, inverse, batch, src, dst):
         """Every tile transformed where it lies: one MIFFT_PASS_ND launch over batch * tiles transforms with the parent's pitches."""
         ctx = self._context
         tx, ty, tz = self._xyz
@@ -567,7 +509,7 @@ class GenericFFTPlan(object):
                     "mifft_launch_nd_tiled_split")
         else:
             N.check(N.lib.mifft_launch_nd_tiled(ctypes.byref(d), ctypes.byref(t), src[0], dst[0], ctx.stream_handle()), "mifft_launch_nd_tiled")
-        return self._epilogue(wait_for_finish)
+        return epilogue(self, wait)
 
     def _inner_plans(self):
         plans = [self._ndplan] if self._ndplan is not None else []

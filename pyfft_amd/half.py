@@ -25,6 +25,7 @@ import numpy
 
 from . import _debug as D
 from . import _native as N
+from .extplan import ExtPlan, buffer_nbytes
 from .plan import normalize_shape, on_plan_device, _twiddle_table
 
 _COMPLEX64 = numpy.dtype(numpy.complex64)
@@ -105,17 +106,9 @@ def _check_dtype(obj, what):
                          "float16, torch complex32 or float16)" % (what, dt))
 
 
-def _buffer_nbytes(obj):
-    nb = getattr(obj, "nbytes", None)
-    if isinstance(nb, (int, numpy.integer)):
-        return int(nb)
-    if hasattr(obj, "data_ptr") and hasattr(obj, "numel") and hasattr(obj, "element_size"):
-        return int(obj.numel()) * int(obj.element_size())
-    return None
-
-
-class HalfFFTPlan(object):
-    """complex32 plan: see the module docstring."""
+class HalfFFTPlan(ExtPlan):
+    """complex32 plan: see the module docstring.  Of ExtPlan's state it uses the capture flag only: no inner plan and no batch-sized
+    scratch, so _capture_keepalive stays empty and close() only finishes."""
 
     @staticmethod
     def validate(shape, dtype="complex32", normalize=True, wait_for_finish=None, fast_math=True, scale=1.0):
@@ -127,25 +120,19 @@ class HalfFFTPlan(object):
         HalfFFTPlan.validate(shape, dtype)
         self._dims = half_dims(shape)
         self._size = self._dims[0] * self._dims[1] * self._dims[2]
-        self._context = context
+        ExtPlan.__init__(self, context, wait_for_finish)
         self._normalize = normalize
         self._scale = float(scale)
-        self._wait_for_finish = wait_for_finish
-        self._captured = False
-        self._capture_keepalive = []     # (always empty: the plan owns no batch-sized scratch; the attribute the other plans have)
         self._tables = []
         on_plan_device(HalfFFTPlan._build)(self)
 
     def _build(self):
-        ctx = self._context
         self._tw = []
         for n in self._dims:
             if n > 1:
-                host = numpy.ascontiguousarray(_twiddle_table(n, n, 1, _COMPLEX64))
-                mem = ctx.allocate_raw(host.nbytes)
-                ctx.upload(mem, host)
+                mem = self._upload(_twiddle_table(n, n, 1, _COMPLEX64))
                 self._tables.append(mem)
-                self._tw.append(ctx.pointer_of(mem))
+                self._tw.append(self._context.pointer_of(mem))
             else:
                 self._tw.append(None)
 
@@ -186,32 +173,18 @@ class HalfFFTPlan(object):
         need = batch * self._size * 4
         for what, obj in (("input", data_in), ("output", data_out)):
             _check_dtype(obj, what)
-            nb = _buffer_nbytes(obj)
+            nb = buffer_nbytes(obj)
             if nb is not None and nb < need:
                 raise ValueError("pyfft_amd: complex32 plan %s buffer holds %d bytes, batch %d needs %d" % (what, nb, batch, need))
         src, dst = ctx.pointer_of(data_in), ctx.pointer_of(data_out)
         if src != dst and src < dst + need and dst < src + need:
             raise ValueError("pyfft_amd: partially overlapping buffers (in place is the same buffer on both sides)")
-        ctx.createQueue((data_in, data_out))
-        wait = self._wait_for_finish if wait_for_finish is None else wait_for_finish
-        capturing = ctx.capturing()
-        if capturing and wait:
-            raise RuntimeError("pyfft_amd: execute() on a capturing stream cannot wait for the result: build the plan with stream= "
-                               "(or wait_for_finish=False), or pass wait_for_finish=False to this call")
-        ctx.order_scratch(capturing)
-        if capturing:
-            # the graph bakes in the table addresses: an open hip.Graph keeps the plan alive
-            from .hip import Graph
-            self._captured = True
-            Graph.retain(self)
+        wait, capturing = self._open((data_in, data_out), wait_for_finish)
+        self._stream_step(capturing)
         x, y, z = self._dims
         N.check(N.lib.mifft_launch_half(x, y, z, self.variant(batch), 1 if inverse else 0, batch, src, dst, self._tw[0], self._tw[1], self._tw[2],
                                         self._factor(inverse), ctx.stream_handle()), "mifft_launch_half")
-        if wait:
-            self.finish()
-            return None
-        ctx.flush()
-        return ctx.getQueue()
+        return self._epilogue(wait)
 
     def execute(self, data_in, data_out=None, inverse=False, batch=1, wait_for_finish=None):
         """execute(a) in place, execute(a, b) out of place; batch transforms one after the other."""
@@ -219,16 +192,5 @@ class HalfFFTPlan(object):
             data_out = data_in
         return self._execute(wait_for_finish, bool(inverse), batch, data_in, data_out)
 
-    @on_plan_device
-    def finish(self):
-        self._context.wait()
-
     def check(self):
         """(Nothing asynchronous to report: one launch, no dependency counters.)"""
-
-    def close(self):
-        self.finish()
-
-    def release_captured(self):
-        self.finish()
-        self._captured = False

@@ -24,31 +24,17 @@ buffers are not 16-byte aligned (the row kernel's 16-byte loads and stores need 
 import numpy
 
 from . import _native as N
-from .generic import _SubContext
+from .extplan import ExtPlan, buffer_nbytes, pow2_shape
 from .plan import FFTPlan, on_plan_device
-from .real import _buffer_nbytes
 
 KINDS = {"dct": 0, "dst": 1}
-
-
-def _is_pow2(n):
-    return n >= 1 and (n & (n - 1)) == 0
 
 
 def r2r_params(shape, dtype, r2r, ortho=False, normalize=True):
     """(numpy-order shape, precision, real dtype, kind) of an r2r plan, or a ValueError naming r2r."""
     if not isinstance(r2r, str) or r2r not in KINDS:
         raise ValueError("pyfft_amd: r2r must be \"dct\" or \"dst\", not %r" % (r2r,))
-    if isinstance(shape, (int, numpy.integer)) and not isinstance(shape, bool):
-        shape = (shape,)
-    if not isinstance(shape, tuple) or not 1 <= len(shape) <= 3:
-        raise ValueError("pyfft_amd: r2r=: wrong shape")
-    for v in shape:
-        if not isinstance(v, (int, numpy.integer)) or isinstance(v, bool) or v < 1:
-            raise ValueError("pyfft_amd: r2r=: wrong shape")
-    shape = tuple(int(v) for v in shape)
-    if not all(_is_pow2(v) for v in shape):
-        raise ValueError("pyfft_amd: r2r=: array dimensions must be powers of two")
+    shape = pow2_shape(shape, "pyfft_amd: r2r=: wrong shape", "pyfft_amd: r2r=: array dimensions must be powers of two")
     if "complex32" in str(dtype) or "float16" in str(dtype) or (isinstance(dtype, str) and dtype.lower() in ("chalf", "half")):
         raise ValueError("pyfft_amd: r2r= has no half-precision form (float32 or float64)")
     if ortho and not normalize:
@@ -142,7 +128,7 @@ def row_tables(n, inverse, ortho, g, complex_dtype):
     return stage, sep, cx(c * f, s * f)
 
 
-class R2RPlan(object):
+class R2RPlan(ExtPlan):
     """Cosine / sine transform plan: see the module docstring."""
 
     @staticmethod
@@ -153,25 +139,17 @@ class R2RPlan(object):
                  ortho=False):
         self._shape, self._precision, self._dtype, self._kind = r2r_params(shape, dtype, r2r, ortho, normalize)
         self._cdtype = numpy.dtype(numpy.complex64 if self._precision == N.F32 else numpy.complex128)
-        self._context = context
+        ExtPlan.__init__(self, context, wait_for_finish)
         self._normalize = bool(normalize)
         self._ortho = bool(ortho)
         self._scale = float(scale)
-        self._wait_for_finish = wait_for_finish
         self._size = int(numpy.prod(self._shape))
         self._kept = tuple(n for n in self._shape if n > 1)
         self.r2r = r2r
         self.r2r_form = r2r_form_of(self._shape, self._precision)
-        self._sub = _SubContext(context)
-        self._scratch = None
-        self._last_batch = 0
-        self._captured = False
-        self._capture_keepalive = []
         on_plan_device(R2RPlan._build)(self)
 
     def _build(self):
-        ctx = self._context
-        self._inner = None
         self._tw = {}
         self._single = {}
         if not self._kept:
@@ -185,21 +163,12 @@ class R2RPlan(object):
                                   wait_for_finish=False, scale=1.0)
         for inv in (False, True):
             kept, g = global_factor(self._shape, inv, self._ortho, self._normalize, self._scale)
-            host = numpy.ascontiguousarray(tables(kept, inv, self._ortho, g, self._cdtype))
-            buf = ctx.allocate_raw(host.nbytes)
-            ctx.upload(buf, host)
-            self._tw[inv] = buf
+            self._tw[inv] = self._upload(tables(kept, inv, self._ortho, g, self._cdtype))
         self._row = {}
         if self.r2r_form == "fused_row":
             for inv in (False, True):
                 g = global_factor(self._shape, inv, self._ortho, self._normalize, self._scale)[1]
-                bufs = []
-                for host in row_tables(self._kept[0], inv, self._ortho, g, self._cdtype):
-                    host = numpy.ascontiguousarray(host)
-                    buf = ctx.allocate_raw(host.nbytes)
-                    ctx.upload(buf, host)
-                    bufs.append(buf)
-                self._row[inv] = bufs
+                self._row[inv] = [self._upload(host) for host in row_tables(self._kept[0], inv, self._ortho, g, self._cdtype)]
 
     @property
     def kernel(self):
@@ -215,26 +184,10 @@ class R2RPlan(object):
 
     # ------------------------------------------------------------------------------------
     def _prepare(self, batch, composed=True):
-        """Plan-owned scratch of the packed array for the composed form, sized by batch (kept alive for a graph that recorded the
-        previous one)."""
-        if not composed or not self._kept or (batch == self._last_batch and self._scratch is not None):
-            return
-        if self._context.capturing():
-            raise RuntimeError("pyfft_amd: execute() on a capturing stream needs one eager execute() of the same batch first")
-        self._release_scratch()
-        self._scratch = self._context.allocate(batch * self._size * self._dtype.itemsize)
-        self._last_batch = batch         # (committed only now: after a failed allocation the plan is as close() leaves it)
-
-    def _release_scratch(self):
-        """Let go of the scratch: to the keep-alive list once a graph has recorded an execute (it replays on it); else, where it came
-        from a mempool, only after the plan's own asynchronous executes have finished with it (hipFree does that waiting itself)."""
-        if self._scratch is not None:
-            if self._captured:
-                self._capture_keepalive.append(self._scratch)
-            else:
-                self._context.wait_scratch()
-        self._scratch = None
-        self._last_batch = 0
+        """Scratch of the packed array for the composed form.  The one-launch route (composed=False) and an item of one point leave
+        the scratch state alone: a fused execute at another batch neither releases the composed scratch nor records its batch."""
+        if composed and self._kept:
+            self._size_scratch(batch, batch * self._size * self._dtype.itemsize)
 
     def _step(self, post, inverse, batch, src, dst, scale=1.0, single=False):
         d = N.MifftR2rStep()
@@ -257,7 +210,7 @@ class R2RPlan(object):
     def _check_buffers(self, batch, data_in, data_out):
         need = batch * self._size * self._dtype.itemsize
         for what, obj in (("input", data_in), ("output", data_out)):
-            nb = _buffer_nbytes(obj)
+            nb = buffer_nbytes(obj)
             if nb is not None and nb < need:
                 raise ValueError("pyfft_amd: r2r plan %s buffer holds %d bytes, batch %d needs %d" % (what, nb, batch, need))
         ptr = self._context.pointer_of
@@ -274,19 +227,10 @@ class R2RPlan(object):
             raise ValueError("batch must be positive")
         self.check()
         src, dst = self._check_buffers(batch, data_in, data_out)
-        ctx.createQueue((data_in, data_out))
-        wait = self._wait_for_finish if wait_for_finish is None else wait_for_finish
-        capturing = ctx.capturing()
-        if capturing and wait:
-            raise RuntimeError("pyfft_amd: execute() on a capturing stream cannot wait for the result: build the plan with stream= "
-                               "(or wait_for_finish=False), or pass wait_for_finish=False to this call")
+        wait, capturing = self._open((data_in, data_out), wait_for_finish)
         fused = self.r2r_form == "fused_row" and (src | dst) % 16 == 0
         self._prepare(batch, composed=not fused)
-        ctx.order_scratch(capturing)
-        if capturing:
-            from .hip import Graph
-            self._captured = True
-            Graph.retain(self)
+        self._stream_step(capturing)
         if not self._kept:
             self._step(inverse, inverse, batch, src, dst, self._single[inverse], single=True)
         elif fused:
@@ -299,11 +243,7 @@ class R2RPlan(object):
             if self._inner is not None:
                 self._inner.execute(z, inverse=inverse, batch=batch, wait_for_finish=False)
             self._step(True, inverse, batch, z, dst)
-        if wait:
-            self.finish()
-            return None
-        ctx.flush()
-        return ctx.getQueue()
+        return self._epilogue(wait)
 
     def execute(self, data_in, data_out=None, *more, inverse=False, batch=1, wait_for_finish=None):
         """execute(x, y) forward (type II), execute(y, x, inverse=True) inverse (type III); data_out None: in place."""
@@ -318,37 +258,3 @@ class R2RPlan(object):
         if data_out is None:
             data_out = data_in
         return self._execute(wait_for_finish, bool(inverse), batch, data_in, data_out)
-
-    # ------------------------------------------------------------------------------------
-    @on_plan_device
-    def finish(self):
-        """Wait for the plan's stream, then raise if the inner plan reported invalid results."""
-        self._context.wait()
-        if self._inner is not None:
-            self._inner.finish()
-
-    @on_plan_device
-    def check(self):
-        """Non-blocking: raise if a completed asynchronous execute() of the inner plan reported invalid results."""
-        if self._inner is not None:
-            self._inner.check()
-
-    def close(self):
-        try:
-            self.finish()
-        finally:
-            self._release_scratch()
-            if self._inner is not None:
-                self._inner.close()
-
-    def release_captured(self):
-        self.finish()
-        self._capture_keepalive = []
-        self._captured = False
-        if self._inner is not None:
-            self._inner.release_captured()
-
-    # introspection (tests, tools/dct_bench.py)
-    @property
-    def inner_plan(self):
-        return self._inner

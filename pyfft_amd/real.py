@@ -26,26 +26,13 @@ stream (a capture records a linear graph).
 import numpy
 
 from . import _native as N
-from .generic import _SubContext
+from .extplan import ExtPlan, buffer_nbytes, pow2_shape
 from .plan import FFTPlan, on_plan_device, _twiddle_table
-
-
-def _is_pow2(n):
-    return n >= 1 and (n & (n - 1)) == 0
 
 
 def real_params(shape, dtype):
     """(numpy-order shape, precision, real dtype, complex dtype) of a real plan, or ValueError."""
-    if isinstance(shape, (int, numpy.integer)) and not isinstance(shape, bool):
-        shape = (shape,)
-    if not isinstance(shape, tuple) or not 1 <= len(shape) <= 3:
-        raise ValueError("Wrong shape")
-    for v in shape:
-        if not isinstance(v, (int, numpy.integer)) or isinstance(v, bool) or v < 1:
-            raise ValueError("Wrong shape")
-    shape = tuple(int(v) for v in shape)
-    if not all(_is_pow2(v) for v in shape):
-        raise ValueError("Array dimensions must be powers of two (real=True has no any_size form)")
+    shape = pow2_shape(shape, "Wrong shape", "Array dimensions must be powers of two (real=True has no any_size form)")
     if shape[-1] < 2:
         raise ValueError("real=True: the contiguous axis (the last numpy axis) must have at least two points")
     try:
@@ -64,17 +51,7 @@ def spectrum_shape(shape):
     return tuple(shape[:-1]) + (shape[-1] // 2 + 1,)
 
 
-def _buffer_nbytes(obj):
-    """Size of a buffer-like object when it knows it (DeviceArray, torch tensor), else None."""
-    nb = getattr(obj, "nbytes", None)
-    if isinstance(nb, (int, numpy.integer)):
-        return int(nb)
-    if hasattr(obj, "data_ptr") and hasattr(obj, "numel") and hasattr(obj, "element_size"):
-        return int(obj.numel()) * int(obj.element_size())
-    return None
-
-
-class RealFFTPlan(object):
+class RealFFTPlan(ExtPlan):
     """Real-input plan: see the module docstring."""
 
     @staticmethod
@@ -83,10 +60,9 @@ class RealFFTPlan(object):
 
     def __init__(self, context, shape, dtype=numpy.float32, normalize=True, wait_for_finish=None, fast_math=True, scale=1.0):
         self._shape, self._precision, self._rdtype, self._cdtype = real_params(shape, dtype)
-        self._context = context
+        ExtPlan.__init__(self, context, wait_for_finish)
         self._normalize = normalize
         self._scale = float(scale)
-        self._wait_for_finish = wait_for_finish
         self._size = int(numpy.prod(self._shape))
         nx = self._shape[-1]
         self._nx = nx
@@ -98,52 +74,23 @@ class RealFFTPlan(object):
         self._spec_points = self._size // nx * (nx // 2 + 1)
         # 1-D rows whose n / 2 has a ROW kernel: one launch (mifft_launch_real_row); everything else: inner complex plan + separation
         self._real_form = "fused_row" if len(self._shape) == 1 and N.lib.mifft_real_row_supported(self._precision, nx) == 0 else "composed"
-        self._sub = _SubContext(context)
-        self._scratch = None
-        self._last_batch = 0
-        self._captured = False
-        self._capture_keepalive = []
         on_plan_device(RealFFTPlan._build)(self)
 
     def _build(self):
-        ctx = self._context
         # the complex transform of the packed data: scale 1, no normalisation (the separation / packing launch applies the real plan's)
-        self._inner = None
         self._tw_half = None
         if self._real_form == "fused_row":
             L = self._nx // 2
-            host = numpy.ascontiguousarray(_twiddle_table(L, L, 1, self._cdtype))
-            self._tw_half = ctx.allocate_raw(host.nbytes)
-            ctx.upload(self._tw_half, host)
+            self._tw_half = self._upload(_twiddle_table(L, L, 1, self._cdtype))
         elif self._packed_points > 1:
             packed = self._packed if len(self._packed) > 1 else self._packed[0]
             self._inner = FFTPlan(self._sub, packed, dtype=self._cdtype, normalize=False, wait_for_finish=False, scale=1.0)
-        host = numpy.ascontiguousarray(_twiddle_table(self._nx, self._nx // 2 + 1, 1, self._cdtype))
-        self._tw = ctx.allocate_raw(host.nbytes)
-        ctx.upload(self._tw, host)
+        self._tw = self._upload(_twiddle_table(self._nx, self._nx // 2 + 1, 1, self._cdtype))
 
     # ------------------------------------------------------------------------------------
     def _prepare(self, batch):
-        """Plan-owned scratch of the packed spectrum, sized by batch (kept alive for a graph that recorded the previous one)."""
-        if batch == self._last_batch:
-            return
-        if self._inner is not None and batch != self._last_batch and self._context.capturing():
-            raise RuntimeError("pyfft_amd: execute() on a capturing stream needs one eager execute() of the same batch first")
-        self._release_scratch()
-        if self._inner is not None:
-            self._scratch = self._context.allocate(batch * self._packed_points * self._cdtype.itemsize)
-        self._last_batch = batch         # (committed only now: after a failed allocation the plan is as close() leaves it)
-
-    def _release_scratch(self):
-        """Let go of the scratch: to the keep-alive list once a graph has recorded an execute (it replays on it); else, where it came
-        from a mempool, only after the plan's own asynchronous executes have finished with it (hipFree does that waiting itself)."""
-        if self._scratch is not None:
-            if self._captured:
-                self._capture_keepalive.append(self._scratch)
-            else:
-                self._context.wait_scratch()
-        self._scratch = None
-        self._last_batch = 0
+        """Scratch of the packed spectrum, where an inner plan runs on it (with the batch unchanged it then always exists)."""
+        self._size_scratch(batch, batch * self._packed_points * self._cdtype.itemsize if self._inner is not None else None)
 
     def _post(self, inverse, batch, src, dst, scale):
         d = N.MifftRealPost()
@@ -166,7 +113,7 @@ class RealFFTPlan(object):
         need_in = batch * (self._spec_points * cs if inverse else self._size * rs)
         need_out = batch * (self._size * rs if inverse else self._spec_points * cs)
         for what, obj, need in (("input", data_in, need_in), ("output", data_out, need_out)):
-            nb = _buffer_nbytes(obj)
+            nb = buffer_nbytes(obj)
             if nb is not None and nb < need:
                 raise ValueError("pyfft_amd: real plan %s buffer holds %d bytes, batch %d needs %d" % (what, nb, batch, need))
 
@@ -192,18 +139,9 @@ class RealFFTPlan(object):
         if real_ptr % need or spec_ptr % cs:
             raise ValueError("pyfft_amd: real plan bases must be aligned: the real side to %d bytes, the spectrum to %d (one complex "
                              "number)" % (need, cs))
-        ctx.createQueue((data_in, data_out))
-        wait = self._wait_for_finish if wait_for_finish is None else wait_for_finish
-        capturing = ctx.capturing()
-        if capturing and wait:
-            raise RuntimeError("pyfft_amd: execute() on a capturing stream cannot wait for the result: build the plan with stream= "
-                               "(or wait_for_finish=False), or pass wait_for_finish=False to this call")
+        wait, capturing = self._open((data_in, data_out), wait_for_finish)
         self._prepare(batch)
-        ctx.order_scratch(capturing)
-        if capturing:
-            from .hip import Graph
-            self._captured = True
-            Graph.retain(self)
+        self._stream_step(capturing)
         if self._real_form == "fused_row":
             factor = self._scale if not inverse else 1.0 / ((self._size if self._normalize else 1.0) * self._scale)
             N.check(N.lib.mifft_launch_real_row(self._precision, self._nx, 1 if inverse else 0, batch, src, dst, ptr(self._tw_half), ptr(self._tw),
@@ -223,11 +161,7 @@ class RealFFTPlan(object):
                 z = ptr(self._scratch)
                 self._post(True, batch, src, z, factor)
                 self._inner.execute(z, dst, inverse=True, batch=batch, wait_for_finish=False)
-        if wait:
-            self.finish()
-            return None
-        ctx.flush()
-        return ctx.getQueue()
+        return self._epilogue(wait)
 
     def execute(self, data_in, data_out=None, *more, inverse=False, batch=1, wait_for_finish=None):
         """execute(real_in, spec_out) forward, execute(spec_in, real_out, inverse=True) inverse; batch items one after the other."""
@@ -244,40 +178,7 @@ class RealFFTPlan(object):
             raise ValueError("pyfft_amd: real plans are out of place only: execute(data_in, data_out)")
         return self._execute(wait_for_finish, bool(inverse), batch, data_in, data_out)
 
-    # ------------------------------------------------------------------------------------
-    @on_plan_device
-    def finish(self):
-        """Wait for the plan's stream, then raise if the inner plan reported invalid results."""
-        self._context.wait()
-        if self._inner is not None:
-            self._inner.finish()
-
-    @on_plan_device
-    def check(self):
-        """Non-blocking: raise if a completed asynchronous execute() of the inner plan reported invalid results."""
-        if self._inner is not None:
-            self._inner.check()
-
-    def close(self):
-        try:
-            self.finish()
-        finally:
-            self._release_scratch()
-            if self._inner is not None:
-                self._inner.close()
-
-    def release_captured(self):
-        self.finish()
-        self._capture_keepalive = []
-        self._captured = False
-        if self._inner is not None:
-            self._inner.release_captured()
-
-    # introspection (tests, tools/real_bench.py)
-    @property
-    def inner_plan(self):
-        return self._inner
-
+    # introspection (tests, tools/real_bench.py; inner_plan: ExtPlan)
     @property
     def real_side_alignment(self):
         """Bytes the base of the real side must be aligned to: 16 where the inner complex plan reads or writes it, one complex number

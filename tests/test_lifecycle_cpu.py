@@ -11,7 +11,7 @@ step failing, for every k the step has, then at B2 again with a healthy pool:
   * scratch that came from a pool is let go of only after wait_scratch(), and never waited for once a graph keeps it.
 
 GenericFFTPlan also refuses, on a context that is capturing, an execute that would allocate: before the pool is asked.
-HalfFFTPlan owns no scratch and has no such step.
+FirPlan's step is filter_spectrum's (its execute needs no scratch).  HalfFFTPlan owns no scratch and has no such step.
 """
 import numpy
 import pytest
@@ -83,6 +83,11 @@ def _r2r(shape, dtype):
     return lambda ctx: R2RPlan(ctx, shape, dtype=dtype, r2r="dct")
 
 
+def _fir(dtype, real=False):
+    from pyfft_amd.fir import FirPlan
+    return lambda ctx: FirPlan(ctx, 256, dtype=dtype, real=real, taps=33)
+
+
 def _smallest_long():
     top = long_limits(numpy.complex64)[0]
     import ctypes
@@ -143,6 +148,8 @@ DRIVES = [
     _Drive("real-composed-f64", _real((1 << 17,), numpy.float64), lambda b: [b * (1 << 16) * 16]),
     _Drive("conv-real-composed", _conv((8, 16), numpy.float32), lambda b: [b * 8 * 9 * 8]),
     _Drive("r2r-composed", _r2r((8, 8), numpy.float64), lambda b: [b * 64 * 8]),
+    _Drive("fir-filter-spectrum-c64", _fir(numpy.complex64), lambda b: [b * 256 * 8]),
+    _Drive("fir-filter-spectrum-f32-real", _fir(numpy.float32, real=True), lambda b: [b * 256 * 4]),
 ]
 
 
